@@ -1,17 +1,28 @@
 #!/usr/bin/env python3
 """Headline benchmark: PC-SAFT pure-component vapour-pressure solves/s (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path at the KERNEL level (the C ABI `pcs_pure_vle_fast` + `pcs_pure_vle_retry` on
 pre-allocated outputs: fused Helmholtz + Newton/VLE kernel, all-fp64 fallback kernel and the robust pass for rare rows)
 over one batch of `--rows` synthetic state points per GPU (SURVEY.md §8d distribution, seed 2026 + rank), inputs resident
-in HBM.  Rank 0 prints ONE JSON line:
+in HBM.  A plain run sets up, runs W untimed and exactly K timed steps, writes the outputs of the last step if
+`--dump-outputs DIR` is given and prints ONE JSON line (rank 0):
 
   value / ms_per_step   weak scaling, every rank solves its own `--rows` rows and keeps its results: rows are independent,
                         the path has no exchange step (barrier + synchronize on both sides, MAX over ranks);
+  roofline              for the dominant kernel k_pure_vle: algorithmic bytes (81 B/solve) / its launch duration measured
+                        with HIP events on the launch stream inside the timed steps, against the HBM roof as the metric
+                        demands, next to the VALU-issue view that actually bounds this path (profiles/pmc_traffic.json).
+
+`--dump-outputs DIR` (rank 0): what a caller of the timed path receives after its last step, on a fixed, seeded sample of
+DUMP_SAMPLE rows of the batch (all rows when the batch is smaller): DIR/p_sat.npy (Pa, float64), DIR/status.npy (float32,
+0 = solved) and DIR/row_index.npy (the sampled rows, float64), 20 MB in all.
+
+`--full` adds the legs that take runs of their own (`--no-extra` / `--no-cpu-baseline` drop parts of them again):
+
   allgather             N > 1: the same step with the RCCL all-gather that re-assembles (p_sat fp64, status u8) on every
                         rank (north_star), in `--chunks` sub-batches so that the collective of chunk k overlaps the
                         solve of chunk k+1;
@@ -20,9 +31,6 @@ in HBM.  Rank 0 prints ONE JSON line:
   variants              N = 1: the same batch through the all-fp64 kernel (densities returned), forward + Jacobian
                         (what a parameter fit runs) and the Python API (PcSaftPure.vapor_pressure, forward and
                         forward + backward, including its allocations and host synchronisation);
-  roofline              for the dominant kernel k_pure_vle: algorithmic bytes (81 B/solve) / its launch duration measured
-                        with HIP events on the launch stream, against the HBM roof as the metric demands, next to the
-                        VALU-issue view that actually bounds this path (profiles/pmc_traffic.json);
   cpu_baseline          N = 1: the CPU oracle (own port; the reference's Rust/feos path cannot be built here) on the host
                         cores, bounded sample.
 """
@@ -39,6 +47,8 @@ if ROOT not in sys.path:
 
 BYTES_PER_SOLVE = 81  # 64 B parameters + 8 B T read, 8 B p_sat + 1 B status written
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 20  # rows written by --dump-outputs: 8 B p_sat + 4 B status + 8 B row index each
+DUMP_SEED = 7
 
 
 def parse():
@@ -48,11 +58,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows", type=int, default=10_000_000, help="state points per GPU per step (weak) / global batch (strong)")
     ap.add_argument("--chunks", type=int, default=4, help="sub-batches per step of the all-gather legs (gather/solve overlap)")
-    ap.add_argument("--no-extra", action="store_true", help="headline leg only (no all-gather / strong / variants legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (seeded sample of the batch) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure: all-gather / strong (N > 1), variants and CPU baseline "
+                         "(N = 1)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no all-gather / strong / variants legs")
     ap.add_argument("--force-gather", action="store_true",
                     help="--gpus 1 only: initialise RCCL at world size 1 and run the chunk-overlapped all-gather leg on it "
                          "(proves the backend, the stream hand-off and the message-size logic; no scaling number)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=40_000_000, help="upper bound on the rows of the CPU baseline sample")
     return ap.parse_args()
 
@@ -77,6 +92,22 @@ def load_pmc(rows):
     except Exception:
         pass
     return {}
+
+
+def dump_outputs(out_dir, plan):
+    """--dump-outputs: the plan's outputs as left by the last step (p_sat, status) on a fixed, seeded sample of rows."""
+    import numpy as np
+    import torch
+
+    if plan.n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(plan.n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(plan.n)
+    sel = torch.from_numpy(idx).to(plan.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "p_sat.npy"), plan.p_sat.index_select(0, sel).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "status.npy"), plan.status.index_select(0, sel).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -151,8 +182,11 @@ def main():
 
     dt = timed(step_headline)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan)
     fails = int(plan.status.sum().item())
     fallback_rows, retry_rows = plan.retry_count()
+    extras = args.full and not args.no_extra
 
     # ---- sharded legs with the all-gather (N > 1) ---------------------------------------------
     def sharded_leg(Ps, Ts, gather):
@@ -188,7 +222,7 @@ def main():
         return timed(step)
 
     extra = {}
-    if world > 1 and not args.no_extra:
+    if world > 1 and extras:
         t_g = sharded_leg(Pd, Td, True)
         extra["allgather"] = {
             "value": world * rows * steps / t_g, "unit": "solves/s", "ms_per_step": t_g / steps * 1e3, "scaling": "weak",
@@ -219,7 +253,7 @@ def main():
                     "the send buffers, ncclAllGather per chunk on RCCL's stream overlapped with the next chunk's solve). Proves "
                     "the backend path only; multi-GPU scaling is UNMEASURED on this pool (one GPU per box).",
         }
-    if world == 1 and not args.no_extra:
+    if world == 1 and extras:
         variants = {}
         full = native.PureVlePlan(rows, device, want_rho_vl=True)  # all-fp64 kernel k_pure_vle<false>, returns the densities
         t_f = timed(lambda _i: full.run(Pd, Td))
@@ -279,7 +313,7 @@ def main():
                             "pre-allocated outputs, pressure-only kernel",
                 "rows_per_gpu": rows,
                 "global_rows": world * rows,
-                "parallelism": f"row-sharded x{world}, no data-path collective in `value` (see `allgather` / `strong`)",
+                "parallelism": f"row-sharded x{world}, no data-path collective in `value` (with --full see `allgather` / `strong`)",
                 "seed": 2026,
                 "failed_rows_rank0": fails,
                 "fp64_fallback_rows_rank0": fallback_rows,
@@ -316,7 +350,7 @@ def main():
             },
         }
         line.update(extra)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # OpenMP threads = CPUs this process may use (affinity mask capped by the cgroup quota)
             from oracle import pyoracle as orc
 
