@@ -10,7 +10,8 @@ OUT = os.path.join(HERE, "libpcsaft_hip.so")
 SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1"]), ("pure_kernels.hip", "pure_kernels_b.o", ["-DPCS_PURE_PART=2"]),
            ("pure_robust.hip", "pure_robust.o", []), ("compact_kernels.hip", "compact_kernels.o", []),
            ("mix_kernels.hip", "mix_kernels.o", []), ("mixn_kernels.hip", "mixn_kernels.o", []),
-           ("gc_kernels.hip", "gc_kernels.o", []), ("gc_gradient.hip", "gc_gradient.o", [])]
+           ("gc_kernels.hip", "gc_kernels.o", []), ("gc_gradient.hip", "gc_gradient.o", []),
+           ("stability_kernels.hip", "stability_kernels.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,
@@ -39,7 +40,7 @@ RELAXED_SOURCES = {"pure_kernels.hip"}
 # 1.74 ms, gc dew 4.28 -> 4.17 ms, dew unchanged (scripts/dev/ab_mix.py / ab_gc.py); the status masks are identical and the
 # results move by <= 6.4e-13 relative.  NaN / infinity semantics stay IEEE (no -fno-honor-*), which the failure detection needs.
 GUARDED = ["-DPCS_FAST_LOG=2", "-DPCS_FAST_RCP=2", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math"]
-GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip"}
+GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip", "stability_kernels.hip"}  # + the stability analysis (NaN / inf outcomes)
 RESOURCES = os.path.join(HERE, "build", "resources.json")  # per-kernel register / stack report of the last build
 
 

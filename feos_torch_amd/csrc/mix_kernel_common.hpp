@@ -1,0 +1,48 @@
+// Helpers shared by the binary-mixture translation units (mix_kernels.hip, stability_kernels.hip): the model struct the
+// solvers are instantiated on, the row load and the class key of a parameter row.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mix_model.hpp"
+
+namespace {
+
+using namespace pcs;
+
+struct MixModel {
+    MixCoef<double> c;
+    template <class R> PCS_DEV R a(const R& r0, const R& r1) const { return mix_a<double, R>(c, r0, r1); }
+    template <class R, class Z> PCS_DEV R a_z(const R& r0, const R& r1, const Z& zeta3) const { return mix_a_z<double, R, Z>(c, r0, r1, zeta3); }
+    PCS_DEV double packing(double x0, double x1) const { return x0 * c.zk[3][0] + x1 * c.zk[3][1]; }
+};
+
+__device__ __forceinline__ void load_mix_row(const double* __restrict__ params, const double* __restrict__ kij,
+                                             int64_t i, double par[16], double& k0, double& k1) {
+    const double2* src = reinterpret_cast<const double2*>(params + 16 * i);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        double2 v = src[k];
+        par[2 * k] = v.x;
+        par[2 * k + 1] = v.y;
+    }
+    double2 kk = reinterpret_cast<const double2*>(kij)[i];
+    k0 = kk.x;
+    k1 = kk.y;
+}
+
+constexpr int MIX_BINS = 8;
+// association class (none, self, induced, cross: mix_model.hpp) x polarity of a parameter row [2][8]
+__device__ __forceinline__ int mix_bucket(const double* __restrict__ row) {
+    const double na0 = row[6], nb0 = row[7], na1 = row[14], nb1 = row[15];
+    const int associating = (na0 + nb0 != 0.0) + (na1 + nb1 != 0.0);
+    const int self_assoc = (na0 * nb0 != 0.0) + (na1 * nb1 != 0.0);
+    int cls = 0;
+    if (associating == 1 && self_assoc == 1) cls = 1;
+    if (associating == 2 && self_assoc == 1) cls = 2;
+    if (associating == 2 && self_assoc == 2) cls = 3;
+    const int polar = (row[3] != 0.0) || (row[11] != 0.0);
+    return 2 * cls + polar;
+}
+
+}  // namespace

@@ -14,6 +14,7 @@
 #include "mix_solver.hpp"
 #include "mix_solver_sm.hpp"
 #include "mix_jacobian.hpp"
+#include "mix_kernel_common.hpp"
 
 using namespace pcs;
 using namespace pcs_abi;
@@ -22,45 +23,10 @@ namespace {
 
 constexpr int MBLOCK = 128;
 
-struct MixModel {
-    MixCoef<double> c;
-    template <class R> PCS_DEV R a(const R& r0, const R& r1) const { return mix_a<double, R>(c, r0, r1); }
-    template <class R, class Z> PCS_DEV R a_z(const R& r0, const R& r1, const Z& zeta3) const { return mix_a_z<double, R, Z>(c, r0, r1, zeta3); }
-    PCS_DEV double packing(double x0, double x1) const { return x0 * c.zk[3][0] + x1 * c.zk[3][1]; }
-};
-
-__device__ __forceinline__ void load_mix_row(const double* __restrict__ params, const double* __restrict__ kij,
-                                             int64_t i, double par[16], double& k0, double& k1) {
-    const double2* src = reinterpret_cast<const double2*>(params + 16 * i);
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        double2 v = src[k];
-        par[2 * k] = v.x;
-        par[2 * k + 1] = v.y;
-    }
-    double2 kk = reinterpret_cast<const double2*>(kij)[i];
-    k0 = kk.x;
-    k1 = kk.y;
-}
-
 // lanes that must be idle before a queue wave refills: the refill code (row load, coefficient set-up) runs for the whole
 // wave (A/B dew 1e6 rows, round 1, one kernel: 1: 7.9 ms, 4: 7.7, 8: 7.5, 16: 7.8; round 3, two kernels: 8: 4.93, 12: 4.84, 16: 4.83, 24: 4.89)
 constexpr int PCS_REFILL_MIN = 16;
 constexpr int REFILL_MIN = PCS_REFILL_MIN;
-
-constexpr int MIX_BINS = 8;
-// association class (none, self, induced, cross: mix_model.hpp) x polarity of a parameter row [2][8]
-__device__ __forceinline__ int mix_bucket(const double* __restrict__ row) {
-    const double na0 = row[6], nb0 = row[7], na1 = row[14], nb1 = row[15];
-    const int associating = (na0 + nb0 != 0.0) + (na1 + nb1 != 0.0);
-    const int self_assoc = (na0 * nb0 != 0.0) + (na1 * nb1 != 0.0);
-    int cls = 0;
-    if (associating == 1 && self_assoc == 1) cls = 1;
-    if (associating == 2 && self_assoc == 1) cls = 2;
-    if (associating == 2 && self_assoc == 2) cls = 3;
-    const int polar = (row[3] != 0.0) || (row[11] != 0.0);
-    return 2 * cls + polar;
-}
 
 template <bool DEW>
 __device__ __forceinline__ void mix_store(int64_t i, int rc, const MixResult& r, double T, double* __restrict__ p_out,

@@ -192,7 +192,7 @@ class _GcBubbleDew(torch.autograd.Function):
     src/gc_pcsaft.rs:103-171)."""
 
     @staticmethod
-    def forward(ctx, dew, model, kab, phi, temperature, molefracs, pressure, box, *segment_parameters):
+    def forward(ctx, dew, model, kab, phi, temperature, molefracs, pressure, box, check, *segment_parameters):
         dev = model.device
         table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
         ph = native._prep(phi, dev, (2,))
@@ -204,7 +204,7 @@ class _GcBubbleDew(torch.autograd.Function):
         box.append(comp)
         value = comp.gather(r["p"])
         needs = [ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]]
-        seg_needs = list(ctx.needs_input_grad[8:])
+        seg_needs = list(ctx.needs_input_grad[9:])
         ctx.saved = False
         if any(needs) or any(seg_needs):
             rows_ok, ph_ok, T_ok, rho4_ok = comp.gather(model.rows), comp.gather(ph), comp.gather(T), comp.gather(r["rho4"])
@@ -226,15 +226,25 @@ class _GcBubbleDew(torch.autograd.Function):
         ctx.devs = (kab.device, phi.device, temperature.device)
         out_device = phi.device
         nans = nans.to(out_device)
+        if check:
+            # stability of the specified phase at the converged solution (liquid for bubble, vapour for dew), on the
+            # compacted rows: aligned with `value`
+            rho4 = comp.gather(r["rho4"])
+            st = native.gc_stability(table, model.S, comp.gather(model.rows), comp.gather(ph), comp.gather(T),
+                                     rho4[:, 0:2] if dew else rho4[:, 2:4],
+                                     order=model._class_order(table) if comp.all_ok else None)["status"]
+            stable = (st == 0).to(out_device)
+            ctx.mark_non_differentiable(nans, stable)
+            return value.to(out_device), nans, stable
         ctx.mark_non_differentiable(nans)
         return value.to(out_device), nans
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, _g):
+    def backward(ctx, g_value, _g, *_g_stable):
         nseg = len(ctx.seg_needs)
         if not ctx.saved:  # nothing the pressure depends on required a gradient
-            return (None,) * (8 + nseg)
+            return (None,) * (9 + nseg)
         jac, agg, rows, ph, T, table, rho4, order = ctx.saved_tensors
         comp, S = ctx.comp, ctx.S
         g = g_value.to(table.device).contiguous()
@@ -252,7 +262,7 @@ class _GcBubbleDew(torch.autograd.Function):
             G = native.gc_segment_gradient(table, S, rows, ph, T, rho4, ctx.dew, gout=g,
                                            order=order if order.numel() == rows.shape[0] else None)
             gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
-        return (None, None, gk, gphi, gT, None, None, None, *gseg)
+        return (None, None, gk, gphi, gT, None, None, None, None, *gseg)
 
 
 class GcPcSaftMix:
@@ -307,21 +317,31 @@ class GcPcSaftMix:
         density = torch.as_tensor(density, dtype=torch.float64)
         return _GcDerivatives.apply(self, self.kab, self.phi, temperature, density, *self._segment_parameters)
 
-    def bubble_point(self, temperature, liquid_molefracs, pressure):
-        """(p [Pa], nans) (:470-490)."""
-        return self._bubble_dew(False, temperature, liquid_molefracs, pressure)
+    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
+        """(p [Pa], nans) (:470-490).  check_stability=True: (p, nans, stable) as PcSaftMix.bubble_point."""
+        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability)
 
-    def dew_point(self, temperature, vapor_molefracs, pressure):
-        """(p [Pa], nans) (:492-512)."""
-        return self._bubble_dew(True, temperature, vapor_molefracs, pressure)
+    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False):
+        """(p [Pa], nans) (:492-512).  check_stability=True: (p, nans, stable) as PcSaftMix.dew_point."""
+        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
 
-    def _bubble_dew(self, dew, temperature, molefracs, pressure):
+    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
         box = []
         # mole fractions and initial pressure do not enter the reference's final formula (:483-490): no gradient flows to them
-        value, nans = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure), box,
-                                         *self._segment_parameters)
+        out = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure), box,
+                                 bool(check_stability), *self._segment_parameters)
         self._reduce(box[0])
-        return value, nans
+        return out
+
+    def stability_analysis(self, temperature, density):
+        """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction
+        or autograd graph: (stable bool [N], tpd [N], trial_density [N,2]) as PcSaftMix.stability_analysis."""
+        with torch.no_grad():
+            table = self._table()
+            r = native.gc_stability(table, self.S, self.rows, self.phi, torch.as_tensor(temperature, dtype=torch.float64),
+                                    torch.as_tensor(density, dtype=torch.float64), order=self._class_order(table))
+            out = self.phi.device
+            return (r["status"] == 0).to(out), r["tpd"].to(out), r["rho_trial"].to(out)
 
     def _class_order(self, table):
         """Class order of the model's rows for the kernels' schedule (native.gc_class_order): computed on first use and

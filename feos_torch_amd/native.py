@@ -415,6 +415,28 @@ def mix_derivatives(params, kij, temperature, density):
     return a, p, mu, v
 
 
+def mix_stability(params, kij, temperature, density):
+    """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
+    density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,
+    3 invalid feed)."""
+    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    density = _prep(density, device, (2,))
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij, density=density)
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        tpd = torch.empty(n, dtype=_F64, device=device)
+        rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        rc = L.pcs_mix_stability(_lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature), _lib.ptr(density), n, _lib.ptr(tpd),
+                                 _lib.ptr(rho_trial), _lib.ptr(status), _lib.current_stream_ptr(device))
+        _lib.check(rc, "pcs_mix_stability")
+    return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
+
+
 def _pcsaft_bubble_dew(parameters, kij, temperature, molefracs, pressure, dew):
     parameters = _as_f64(parameters, 3)
     kij = _as_f64(kij, 2)
@@ -550,6 +572,30 @@ def gc_derivatives(table, S, rows, phi, temperature, density):
                                   _lib.current_stream_ptr(device))
         _lib.check(rc, "pcs_gc_derivatives")
     return a, p, mu, v
+
+
+def gc_stability(table, S, rows, phi, temperature, density, order=None):
+    """mix_stability for gc rows (pcs_gc_stability); order: optional class order of the rows (gc_class_order), schedule
+    only.  -> dict(tpd, rho_trial, status)."""
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature = _prep(temperature, device)
+    density = _prep(density, device, (2,))
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi, density=density)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (n,) or order.device != device or not order.is_contiguous()):
+        raise ValueError("order must be a contiguous int32 tensor [n] on the device of the table")
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        tpd = torch.empty(n, dtype=_F64, device=device)
+        rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        rc = L.pcs_gc_stability(_lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi), _lib.ptr(temperature), _lib.ptr(density),
+                                n, _lib.ptr(tpd), _lib.ptr(rho_trial), _lib.ptr(status), _lib.ptr(order),
+                                _lib.current_stream_ptr(device))
+        _lib.check(rc, "pcs_gc_stability")
+    return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
 
 
 def gc_jacobian(table, S, rows, phi, temperature, rho4, dew, order=None):

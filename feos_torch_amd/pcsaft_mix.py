@@ -21,7 +21,7 @@ class _BubbleDew(torch.autograd.Function):
     inside the native call, src/pcsaft.rs:216-231)."""
 
     @staticmethod
-    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, box):
+    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, box, check=False):
         out_device = parameters.device
         dev = native._dev() if not parameters.is_cuda else parameters.device
         par = native._prep(parameters, dev, (2, 8))
@@ -42,12 +42,21 @@ class _BubbleDew(torch.autograd.Function):
         ctx.needs = needs
         ctx.in_devices = (parameters.device, kij.device, temperature.device)
         nans = nans.to(out_device)
+        if check:
+            # stability of the specified phase at the converged solution (liquid for bubble, vapour for dew), on the
+            # compacted rows: aligned with `value`
+            rho4 = comp.gather(r["rho4"])
+            feed = rho4[:, 0:2] if dew else rho4[:, 2:4]
+            st = native.mix_stability(comp.gather(par), comp.gather(k), comp.gather(T), feed)["status"]
+            stable = (st == 0).to(out_device)
+            ctx.mark_non_differentiable(nans, stable)
+            return value.to(out_device), nans, stable
         ctx.mark_non_differentiable(nans)
         return value.to(out_device), nans
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, _g_nans):
+    def backward(ctx, g_value, _g_nans, *_g_stable):
         (jac,) = ctx.saved_tensors
         comp = ctx.comp
         g = g_value.to(jac.device).contiguous()
@@ -59,7 +68,7 @@ class _BubbleDew(torch.autograd.Function):
             gk = comp.expand(jac, g, 16, 2).to(ctx.in_devices[1])
         if ctx.needs[2]:
             gt = comp.expand(jac, g, 18, 1).view(n).to(ctx.in_devices[2])
-        return None, gp, gk, gt, None, None, None
+        return None, gp, gk, gt, None, None, None, None
 
 
 class _MixDerivatives(torch.autograd.Function):
@@ -184,22 +193,41 @@ class PcSaftMix:
             return _MixnDerivatives.apply(self._par, temperature, density)
         return _MixDerivatives.apply(self._par, self.kij, temperature, density)
 
-    def _bubble_dew(self, dew, temperature, molefracs, pressure):
+    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
         if self.ncomp != 2:
             raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
         box = []
         # mole fractions and initial pressure do not enter the reference's final formula (:435-444): no gradient flows to them
-        value, nans = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure), box)
+        out = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure), box,
+                               bool(check_stability))
         self._reduce(box[0])
-        return value, nans
+        return out
 
-    def bubble_point(self, temperature, liquid_molefracs, pressure):
-        """(p [Pa], nans) at T [K], liquid mole fraction of component 1, initial pressure [Pa] (:422-444)."""
-        return self._bubble_dew(False, temperature, liquid_molefracs, pressure)
+    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
+        """(p [Pa], nans) at T [K], liquid mole fraction of component 1, initial pressure [Pa] (:422-444).
+        check_stability=True: (p, nans, stable), stable [bool, aligned with p] = the liquid at the solution passed
+        stability_analysis (False: a metastable or unstable root, e.g. inside a liquid-liquid split).  p, nans, the gradients
+        and the model reduction are those of the default call."""
+        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability)
 
-    def dew_point(self, temperature, vapor_molefracs, pressure):
-        """(p [Pa], nans) at T [K], vapour mole fraction of component 1, initial pressure [Pa] (:446-468)."""
-        return self._bubble_dew(True, temperature, vapor_molefracs, pressure)
+    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False):
+        """(p [Pa], nans) at T [K], vapour mole fraction of component 1, initial pressure [Pa] (:446-468).
+        check_stability=True: (p, nans, stable) with the stability of the vapour at the solution (see bubble_point)."""
+        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
+
+    def stability_analysis(self, temperature, density):
+        """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's
+        rows as they are (no reduction, no autograd graph).  -> (stable bool [N], tpd [N] smallest tangent-plane distance found
+        [kT per mole of trial phase], trial_density [N,2] its trial phase).  Definitions and the status codes behind `stable`:
+        include/pcsaft_hip.h, pcs_mix_stability (tpd = -inf: the feed itself is locally unstable; NaN: invalid feed)."""
+        if self.ncomp != 2:
+            raise Exception("stability analysis is implemented for binary mixtures only")
+        with torch.no_grad():
+            temperature = torch.as_tensor(temperature, dtype=torch.float64)
+            density = torch.as_tensor(density, dtype=torch.float64)
+            r = native.mix_stability(self._par, self.kij, temperature, density)
+            out = self._par.device
+            return (r["status"] == 0).to(out), r["tpd"].to(out), r["rho_trial"].to(out)
 
     def _reduce(self, comp):
         if not comp.all_ok:

@@ -165,6 +165,31 @@ int pcs_mix_derivatives(const double* params, const double* kij, const double* t
                         double* a, double* p, double* mu, double* v, void* stream);
 
 /*
+ * Tangent-plane stability analysis of binary feed states (PcSaftMix.stability_analysis).  Reduced units as for
+ * pcs_mix_derivatives: a(rho_1, rho_2) = residual Helmholtz energy density / kT [A^-3], mu_i = ln rho_i + da/drho_i,
+ * p = sum rho_k - a + sum rho_k da/drho_k.
+ *   Feed: T and partial densities rho^f -> p^f, z_i = rho^f_i / sum rho^f.
+ *   Trial phase: partial densities rho^t at the same T with p(rho^t) = p^f on a mechanically stable root (dp/drho > 0 along
+ *   its composition w_i = rho^t_i / sum rho^t);  tpd(rho^t) = sum_i w_i (mu_i(rho^t) - mu_i(rho^f))  [kT per mole of trial
+ *   phase] = Michelsen's sum_i w_i (ln w_i + ln phi_i(w) - ln z_i - ln phi_i(z)).  A trial with |w_1 - z_1| < 1e-6 and
+ *   |sum rho^t / sum rho^f - 1| < 1e-6 is trivial and never counts.  TPD_TOL = 1e-8.
+ *   params [n,2,8], kij [n,2], temp [n], rho [n,2]   in   (rho: the feed's partial densities, A^-3)
+ *   tpd       [n]     out  (optional) smallest tpd among the non-trivial stationary points the search reached; +inf when it
+ *                          reached none, -inf for status 2, NaN for status 3
+ *   rho_trial [n,2]   out  (optional) partial densities of the trial phase of `tpd` (NaN when there is none)
+ *   status    [n]     out  uint8: 0 stable (no trial with tpd < -TPD_TOL), 1 unstable (one found), 2 locally unstable feed
+ *                          (the Hessian of a + sum rho_i (ln rho_i - 1) in rho is not positive definite; no search),
+ *                          3 invalid feed (non-finite or non-positive density, or p^f <= 0)
+ * Search: Michelsen's successive substitution in ln(w_1 / w_2) with Newton steps where tpd is locally convex, from four
+ * fixed starts (ideal gas at the feed's chemical potentials on the vapour-like root; liquid-like roots rich in either
+ * component, and equimolar).  On a converged bubble / dew point the incipient phase is such a stationary point (tpd ~ 0).  Rows of
+ * pcs_mix_bubble_dew that converged through the stagnation exit (|d mu| up to 1e-3) may come out unstable: their
+ * incipient phase does not have equal chemical potentials.
+ */
+int pcs_mix_stability(const double* params, const double* kij, const double* temp, const double* rho, int64_t n,
+                      double* tpd, double* rho_trial, uint8_t* status, void* stream);
+
+/*
  * n-component mixtures: PcSaftMix.derivatives for parameters [n, ncomp, 8] WITHOUT k_ij -- the parts of the
  * reference's model that are written for any number of components (feos_torch/pcsaft_mix.py:31-154: hard sphere, hard chain,
  * dispersion, dipoles, self association of ONE associating component; "kij can only be used for binary mixtures", :75-76, and two
@@ -224,6 +249,12 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
 /* GcPcSaftMix.derivatives (feos_torch/gc_pcsaft.py:443-468): a, p, mu [n,2], v [n,2] at rho [n,2]. */
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream);
+
+/* GcPcSaftMix.stability_analysis: pcs_mix_stability for gc rows (table / rows / phi as for pcs_gc_bubble_dew).  order: as
+ * for pcs_gc_bubble_dew (optional; only the schedule changes, results are identical). */
+int pcs_gc_stability(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                     const double* rho, int64_t n, double* tpd, double* rho_trial, uint8_t* status,
+                     const int32_t* order, void* stream);
 
 /*
  * Gradient of the gc bubble / dew pressure [Pa] at the converged densities rho4:

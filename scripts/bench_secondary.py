@@ -4,6 +4,8 @@ with HIP events on the launch stream, inputs resident in HBM.
   config 3: PcSaftPure liquid_density + equilibrium_liquid_density, batch 1e7
   config 4: PcSaftMix bubble / dew point, batch 1e6
   config 5: GcPcSaftMix bubble / dew point, batch 1e6
+  stability: tangent-plane stability analysis (pcs_mix_stability / pcs_gc_stability) of the converged bubble and dew
+             feeds of configs 4 and 5 (the specified phase at the solution), batch 1e6 minus the failed rows
 Prints one JSON object per config."""
 import json
 import os
@@ -30,6 +32,13 @@ def timed(fn, reps=5):
         e0.record(); out = fn(); e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
     return float(np.median(ts)), out
+
+
+def stability_feeds(r, dew):
+    """(row indices, feed partial densities) of the converged rows: the specified phase of the solution"""
+    ok = torch.nonzero(~r["status"]).view(-1)
+    rho4 = r["rho4"][ok]
+    return ok, (rho4[:, 0:2] if dew else rho4[:, 2:4]).contiguous()
 
 
 which = sys.argv[1:] or ["3", "4", "5"]
@@ -70,3 +79,33 @@ if "5" in which:
     for dew in (False, True):
         ms, r = timed(lambda: native.gc_bubble_dew(tab, len(ident), rows, phi, T, x, p0, dew, order=order), reps=3)
         print(json.dumps({"config": f"GcPcSaftMix {'dew' if dew else 'bubble'} point batch=1e6", "ms": ms, "rows_per_s": n / ms * 1e3, "failed": int(r["status"].sum()), "host_encode_s": t_enc}))
+if "stability" in which:
+    n = 1_000_000
+    P, K, T, X, PI = mix_batch(n)
+    a = [d(v) for v in (P, K, T, X, PI)]
+    for dew in (False, True):
+        ok, feed = stability_feeds(native.mix_bubble_dew(*a, dew), dew)
+        Pk, Kk, Tk = a[0][ok].contiguous(), a[1][ok].contiguous(), a[2][ok].contiguous()
+        ms, r = timed(lambda: native.mix_stability(Pk, Kk, Tk, feed), reps=3)
+        cnt = torch.bincount(r["status"].long(), minlength=4).tolist()
+        print(json.dumps({"config": f"PcSaftMix stability of the {'dew' if dew else 'bubble'} feeds batch={len(ok)}", "ms": ms,
+                          "rows_per_s": len(ok) / ms * 1e3, "status_counts": cnt, "flagged_fraction": 1.0 - cnt[0] / len(ok)}))
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    from feos_torch_amd.gc_pcsaft import encode_rows_device
+    rows = encode_rows_device(ident, b["segment_lists"], b["bond_lists"], "cuda")
+    seg = torch.tensor(np.stack([v for _, v in table]), dtype=torch.float64)
+    kab = torch.zeros((len(ident), len(ident)), dtype=torch.float64)
+    for s1, s2, k in b["kab_list"]:
+        kab[ident.index(s1), ident.index(s2)] = k; kab[ident.index(s2), ident.index(s1)] = k
+    tab = build_table(seg.cuda(), kab.cuda())
+    phi, T, x, p0 = d(b["phi"]), d(b["T"]), d(b["x"]), d(b["p_init"])
+    order = native.gc_class_order(tab, len(ident), rows)
+    for dew in (False, True):
+        ok, feed = stability_feeds(native.gc_bubble_dew(tab, len(ident), rows, phi, T, x, p0, dew, order=order), dew)
+        rows_ok, phi_ok, T_ok = rows[ok].contiguous(), phi[ok].contiguous(), T[ok].contiguous()
+        order_ok = native.gc_class_order(tab, len(ident), rows_ok)
+        ms, r = timed(lambda: native.gc_stability(tab, len(ident), rows_ok, phi_ok, T_ok, feed, order=order_ok), reps=3)
+        cnt = torch.bincount(r["status"].long(), minlength=4).tolist()
+        print(json.dumps({"config": f"GcPcSaftMix stability of the {'dew' if dew else 'bubble'} feeds batch={len(ok)}", "ms": ms,
+                          "rows_per_s": len(ok) / ms * 1e3, "status_counts": cnt, "flagged_fraction": 1.0 - cnt[0] / len(ok)}))
