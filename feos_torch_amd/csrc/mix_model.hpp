@@ -323,10 +323,10 @@ PCS_DEV R core_terms_z(const C& c, const R& r0, const R& r1, const Z& zeta3, Pac
                  (r0 * r11) * horner_z<4>(c.tj[2], zeta3) + (r11 * r1) * horner_z<4>(c.tj[3], zeta3);
         // phi2 = phi3 = 0 where no polar component is present (pure-component limit next to a polar partner): the
         // quotient's limit is phi2 + O(rho_polar^3) (value and gradient 0, Hessian that of phi2).  The same limit for a TRACE
-        // polar component (|phi2| < 1e-90: partial densities below ~1e-45 of the liquid's): the quotient's second
-        // derivatives carry 1/phi2^3, which overflows fp64 there and turned the Newton steps of dew rows whose incipient
-        // liquid holds ~1e-50 of the polar component into NaN; the neglected phi3 term is O(rho_polar^3) < 1e-135
-        if (fabs(re(phi2)) < 1e-90) a = a + phi2;
+        // polar component (|phi2| < PHI2_TRACE, pcsaft_consts.hpp): the quotient's derivatives carry powers of 1/phi2, which
+        // overflow fp64 there (NaN Newton steps of dew rows whose incipient liquid holds ~1e-50 of the polar component, NaN
+        // gradients of the backward pass at ~1e-44)
+        if (fabs(re(phi2)) < PHI2_TRACE) a = a + phi2;
         else a = a + (phi2 * phi2) * d_recip(phi2 - phi3);
     }
     return a;

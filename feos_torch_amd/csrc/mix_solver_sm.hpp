@@ -465,6 +465,11 @@ struct BdLane {
                 const double dens_i = ri0 + ri1;
                 const double lo = DEW ? rs : dens_i, hi = DEW ? dens_i : rs;
                 if (!(lo < hi * (1.0 - 1e-6))) { newton_failed(); return; }  // trivial solution
+                // a trace component of the specified phase below the normal range of fp64 (z ~ 1e-300 in a dilute dew
+                // vapour): the reciprocal 1 / rho_i of the Newton matrix has overflowed and the rounding of a subnormal
+                // density is far above the tolerances, so the accepted state can be off by ~20 %: the row fails instead
+                // (include/pcsaft_hip.h, 0 < z < 1)
+                if (!(z0 * rs >= 2.2250738585072014e-308 && z1 * rs >= 2.2250738585072014e-308)) { newton_failed(); return; }
                 stage = S_DONE;
                 // converged: the state these two evaluations were taken at is within mx of the solution and the
                 // reference's final formula is second order in that error, so it is applied to them directly (no

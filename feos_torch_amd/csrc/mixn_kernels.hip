@@ -227,7 +227,9 @@ HVD HV<NC + 1, S> mixn_a(const S* par, const S& T, const S* x, S& rs, bool& bad)
         }
         phi2 = phi2 * PI;
         phi3 = phi3 * PI_SQ_43;
-        if (pcs::re(phi2.re) == 0.0) a = a + phi2;  // no polar component present at this state: limit of the quotient (mix_model.hpp)
+        // no polar component present at this state, or only a trace of one (|phi2| < PHI2_TRACE): the limit of the quotient, as
+        // in mix_model.hpp -- its derivatives carry powers of 1/phi2, which overflow fp64 (v = NaN at rho_polar / rho ~ 1e-60)
+        if (fabs(pcs::re(phi2.re)) < PHI2_TRACE) a = a + phi2;
         else a = a + (phi2 * phi2) * hv_recip(phi2 - phi3);
     }
     // association (:118-152): exactly one associating component -> phi_self_assoc (:210-239)

@@ -6,6 +6,12 @@
 
 namespace pcs {
 
+// Dipole term a = phi2^2 / (phi2 - phi3): below |phi2| = PHI2_TRACE (a trace polar component, partial density below ~1e-30 of
+// the phase's) its limit phi2 is taken.  The quotient's k-th derivatives carry 1/phi2^(k+1): the backward pass of v needs the
+// third (1/phi2^4), which overflows fp64 for |phi2| < ~1e-77 (the old threshold 1e-90 was enough for the Hessian only); the
+// neglected term is O(phi3) < 1e-90 in value and O(rho_polar^2) < 1e-60 in mu.
+constexpr double PHI2_TRACE = 1e-60;
+
 constexpr double A0[7] = {0.91056314451539, 0.63612814494991, 2.68613478913903, -26.5473624914884,
                           97.7592087835073, -159.591540865600, 91.2977740839123};
 constexpr double A1[7] = {-0.30840169182720, 0.18605311591713, -2.50300472586548, 21.4197936296668,

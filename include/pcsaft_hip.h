@@ -141,7 +141,9 @@ int pcs_pure_jacobian_vjp(int which, const double* params, const double* temp, c
  *   params  [n,2,8] in    component rows as for the pure model
  *   kij     [n,2]   in    kij[:,0] = k_ij, kij[:,1] = explicit eps_AiBj/k, 0 = combining rule
  *                         (src/pcsaft.rs:163, pcsaft_mix.py:509-516)
- *   temp, z, p_init [n] in    K, -, Pa (p_init = the caller's starting pressure, src/pcsaft.rs:174)
+ *   temp, z, p_init [n] in    K, -, Pa (p_init = the caller's starting pressure, src/pcsaft.rs:174); 0 < z < 1: a row at
+ *                         z = 0 or z = 1 (a pure component, no mixture) fails; a trace amount down to the smallest
+ *                         subnormal either converges to the limit of the dilute solution or fails
  *   p_out   [n]     out   Pa   pcsaft_mix.py:443-444 / :467-468                 (optional)
  *   rho4    [n,4]   out   A^-3 (rhoV_1, rhoV_2, rhoL_1, rhoL_2), src/pcsaft.rs:225-228 (optional)
  *   status  [n]     out   uint8, 1 = failed
@@ -234,7 +236,8 @@ int pcs_mix_jacobian(int dew, const double* params, const double* kij, const dou
  *                             seg_id [0:16], seg_cnt [16:32], bond_a [32:48], bond_b [48:64],
  *                             bond_cnt [64:80] (count 0 = unused entry)
  *   phi    [n,2]         in   src/gc_pcsaft.rs:30, feos_torch/gc_pcsaft.py:182-185
- *   temp, z, p_init [n]  in   as for pcs_mix_bubble_dew
+ *   temp, z, p_init [n]  in   as for pcs_mix_bubble_dew, 0 < z < 1 included (the same solver: z = 0 or 1 fails, a trace
+ *                             amount either converges to the limit of the dilute solution or fails)
  *   outputs, workspace        as for pcs_mix_bubble_dew
  *   order  [n] int32     in   optional (NULL: rows are bucketed by class inside each workgroup): a permutation of the rows,
  *                             position -> row, normally sorted by model class (association class x polarity) so that a
