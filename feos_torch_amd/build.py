@@ -7,7 +7,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpcsaft_hip.so")
 # (source, object, extra flags).  pure_kernels.hip is compiled twice: part 1 with re-association (pressure-only VLE kernel,
 # Jacobians, C ABI), part 2 without (all-fp64 VLE kernel, liquid density): see the head of the file
-SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1"]), ("pure_kernels.hip", "pure_kernels_b.o", ["-DPCS_PURE_PART=2"]),
+SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_CONST_TABLES"]), ("pure_kernels.hip", "pure_kernels_b.o", ["-DPCS_PURE_PART=2"]),
            ("pure_robust.hip", "pure_robust.o", []), ("compact_kernels.hip", "compact_kernels.o", []),
            ("mix_kernels.hip", "mix_kernels.o", []), ("mixn_kernels.hip", "mixn_kernels.o", []),
            ("gc_kernels.hip", "gc_kernels.o", []), ("gc_gradient.hip", "gc_gradient.o", []),
@@ -29,6 +29,9 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # the same), Jacobian kernels x1.13; the all-fp64 VLE kernel and the liquid-density kernel get SLOWER with it (x0.96, x0.75),
 # hence the two parts.  The explicit fma chains of the logarithm / reciprocal refinements are untouched, and the parity of
 # the kernels against the long-double oracle is unchanged (tests/test_large_parity_gpu.py: 1e-10 on 1e6 rows).
+# -DPCS_CONST_TABLES (part 1 only): polynomial constants of the fp64 logarithm and of the pressure-only fp64 evaluation are read
+# from constant memory into scalar registers instead of being moved into vector registers as literals (dual.hpp, pure_model.hpp):
+# k_pure_vle<true> 0.7388 -> 0.7329 ms per 1e7 rows (scripts/dev/ab_alternate.py).
 RELAXED = ["-fno-honor-nans", "-fno-honor-infinities", "-fno-signed-zeros", "-fno-slp-vectorize", "-DPCS_FAST_RCP", "-DPCS_FAST_LOG",
            "-DPCS_F32_PRESOLVE"]
 REASSOC = ["-fassociative-math", "-freciprocal-math"]  # part 1 of pure_kernels.hip only

@@ -29,6 +29,15 @@ PCS_DEV double d_exp(double x) { return exp(x); }
 // fractions in (0, 1]).
 #ifdef PCS_FAST_LOG
 PCS_DEV double d_recip(double x);
+#ifdef PCS_CONST_TABLES
+// Part 1 of the pure-component unit (build.py): the polynomial's coefficients from constant memory.  As literals each is the
+// addend of an fma and costs two v_mov_b32 into the destination of a v_fmac_f64 (gfx950 has no 64-bit literal operand); read
+// from memory they sit in scalar registers after one scalar load per kernel and are the scalar operand of a v_fma_f64: 12
+// fewer vector instructions per logarithm.  Defined in ONE translation unit only (the variable has a host-side shadow).
+inline __device__ __constant__ double LOG_R[7] = {1.479819860511658591e-01, 1.531383769920937332e-01, 1.818357216161805012e-01,
+                                                  2.222219843214978396e-01, 2.857142874366239149e-01, 3.999999999940941908e-01,
+                                                  6.666666666666735130e-01};
+#endif
 PCS_DEV double d_log(double x) {
     int e = __builtin_amdgcn_frexp_exp(x);
     double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
@@ -38,6 +47,12 @@ PCS_DEV double d_log(double x) {
     const double f = m - 1.0;
     const double s = f * d_recip(m + 1.0);
     const double z = s * s;
+#ifdef PCS_CONST_TABLES
+    const double* K = LOG_R;
+    double R = K[0];
+#pragma unroll
+    for (int i = 1; i < 7; i++) R = __builtin_fma(R, z, K[i]);
+#else
     double R = 1.479819860511658591e-01;
     R = __builtin_fma(R, z, 1.531383769920937332e-01);
     R = __builtin_fma(R, z, 1.818357216161805012e-01);
@@ -45,6 +60,7 @@ PCS_DEV double d_log(double x) {
     R = __builtin_fma(R, z, 2.857142874366239149e-01);
     R = __builtin_fma(R, z, 3.999999999940941908e-01);
     R = __builtin_fma(R, z, 6.666666666666735130e-01);
+#endif
     double r = __builtin_fma((double)e, 0.69314718055994530942, __builtin_fma(s, R * z, s + s));
 #if PCS_FAST_LOG == 2
     // the mixture / gc solvers detect degenerate states by the IEEE results of the library log: keep them

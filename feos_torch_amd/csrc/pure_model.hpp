@@ -272,6 +272,13 @@ PCS_DEV R pure_a(const PureCoef<P>& c, const R& rho) {
 // pre-solve does (pure_f32.hpp): a = rho F(eta) + rho^2 G(eta),
 //   F = m HS - (m-1) ln g,  HS = (4 eta - 3 eta^2) u^2,  HS' = (4 - 2 eta) u^3,  (ln g)' = 3u - w,  u = 1/(1-eta), w = 1/(2-eta)
 //   G = kd1 I1 + kd2 C I2,  C = 1/D,  D = 1 + m A - (m-1) B,  A' = (8 + 20 eta - 4 eta^2) u^5,  B' = q (poly' + 2 poly (u + w)), q = u^2 w^2
+#ifdef PCS_CONST_TABLES
+// The integer constants of A, A', poly, poly' below from constant memory, as the logarithm's (dual.hpp): 16 fewer v_mov_b32
+// per evaluation.
+inline __device__ __constant__ double D1S_K[7] = {8.0, 20.0, -27.0, 12.0, -54.0, 36.0, -8.0};
+#else
+constexpr double D1S_K[7] = {8.0, 20.0, -27.0, 12.0, -54.0, 36.0, -8.0};
+#endif
 template <>
 PCS_DEV D1s pure_a<double, D1s>(const PureCoef<double>& c, const D1s& rho) {
     const double r = rho.v, eta = r * c.ceta;
@@ -282,9 +289,10 @@ PCS_DEV D1s pure_a<double, D1s>(const PureCoef<double>& c, const D1s& rho) {
     const double F = c.m * HS - c.mm1 * LG, F1 = c.m * HS1 - c.mm1 * LG1;
     const D1s e1(eta, 1.0);
     const D1s I1 = horner_eta<7>(c.ai, e1), I2 = horner_eta<7>(c.bi, e1);  // value and eta-derivative
-    const double A = eta * (8.0 - 2.0 * eta) * u4, A1 = (8.0 + eta * (20.0 - 4.0 * eta)) * (u4 * u);
-    const double poly = eta * (20.0 + eta * (-27.0 + eta * (12.0 - 2.0 * eta)));
-    const double poly1 = 20.0 + eta * (-54.0 + eta * (36.0 - 8.0 * eta));
+    const double* K = D1S_K;  // 8, 20, -27, 12, -54, 36, -8
+    const double A = eta * (K[0] - 2.0 * eta) * u4, A1 = (K[0] + eta * (K[1] - 4.0 * eta)) * (u4 * u);
+    const double poly = eta * (K[1] + eta * (K[2] + eta * (K[3] - 2.0 * eta)));
+    const double poly1 = K[1] + eta * (K[4] + eta * (K[5] + K[6] * eta));
     const double q = u2 * (w * w);
     const double B = poly * q, B1 = q * (poly1 + 2.0 * poly * (u + w));
     const double D = 1.0 + c.m * A - c.mm1 * B, D1_ = c.m * A1 - c.mm1 * B1;

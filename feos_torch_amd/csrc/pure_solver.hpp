@@ -173,7 +173,8 @@ PCS_DEV bool vapour_is_physical(double p_star, double rho_v) { return gt0(p_star
 struct VleStep {
     double p_star, p_corr, dl, dv;
 };
-PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv) {
+// il, iv = 1/l.dp, 1/v.dp
+PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv, double il, double iv) {
     VleStep s;
     // d_recip / d_log: the refined hardware reciprocal and the short logarithm where the unit is built with
     // PCS_FAST_RCP / PCS_FAST_LOG (dual.hpp), the IEEE division and library log otherwise
@@ -181,11 +182,13 @@ PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv) {
     double inv_dv = d_recip(inv_v - inv_l);
     s.p_star = -(v.a * inv_v - l.a * inv_l + d_log(rv * inv_l)) * inv_dv;
     double rl_res = l.p - s.p_star, rv_res = v.p - s.p_star;
-    double il = d_recip(l.dp), iv = d_recip(v.dp);
     s.dl = -rl_res * il;
     s.dv = -rv_res * iv;
     s.p_corr = s.p_star + 0.5 * ((rv_res * rv_res) * (inv_v * inv_v) * iv - (rl_res * rl_res) * (inv_l * inv_l) * il) * inv_dv;
     return s;
+}
+PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv) {
+    return vle_step(l, v, rl, rv, d_recip(l.dp), d_recip(v.dp));
 }
 
 // Fast path of the pure VLE: zero-pressure liquid + ideal-gas vapour initialisation, then the
@@ -282,6 +285,9 @@ PCS_DEV int vle_lite_finish(const double* par, double T, bool warm, double rl, d
     Eval le, ve;
     le.dp = (double)dpl32;
     ve.dp = (double)dpv32;
+    // the slopes are fp32 numbers (relative error ~1e-3) that only steer a ~1e-6 step and scale the second-order term of p*
+    // (<= 1e-9 relative): their reciprocals at the fp32 reciprocal's accuracy, not the refined fp64 one
+    const double il = (double)__builtin_amdgcn_rcpf(dpl32), iv = (double)__builtin_amdgcn_rcpf(dpv32);
     // at most LITE_MAX_IT iterations: with the fp32 dp/drho the iteration converges linearly, fast (ratio ~1e-3) on
     // ordinary rows but slowly close to the critical point where dp/drho -> 0 -- those rows go to the all-fp64 path
     for (int it = 0; it < LITE_MAX_IT; it++) {
@@ -290,7 +296,7 @@ PCS_DEV int vle_lite_finish(const double* par, double T, bool warm, double rl, d
             D1s av = pure_a<double, D1s>(c, D1s(rv, 1.0));
             le.a = al.v; le.p = rl - al.v + rl * al.d1;
             ve.a = av.v; ve.p = rv - av.v + rv * av.d1;
-            VleStep s = vle_step(le, ve, rl, rv);
+            VleStep s = vle_step(le, ve, rl, rv, il, iv);
             bool ok = is_finite_bits(s.p_star) && is_finite_bits(s.dl) && is_finite_bits(s.dv);
             double rl_new = rl + s.dl, rv_new = rv + s.dv;
             ok = ok && (rl_new > 0.0) && (rv_new > 0.0) && (rv_new < rl_new);
