@@ -2,7 +2,8 @@
 //
 // Roles of the reference types (feos_torch/dual.py, feos_torch/dual_torch.py):
 //   D2<T>      value + 1st + 2nd derivative along ONE direction     (Dual3, dual.py:5-78)
-//   DN<T,N>    value + N first derivatives                          (parameter tangents; what
+//   D3<T>      value + 1st + 2nd + 3rd derivative along one direction (critical points; the reference has no counterpart)
+//   DN<T,N>    value + N first derivatives                        (parameter tangents; what
 //              torch reverse mode delivers in the reference is delivered forward here)
 //   T2<T>      value, gradient and Hessian in the two partial densities (supersedes DualTensor,
 //              dual_torch.py:4-158, which carries only the volume-mixed second derivatives)
@@ -275,6 +276,61 @@ template <class T, int N> PCS_DEV DN<T, N> d_sqrt(const DN<T, N>& a) { T s = d_s
 template <class T, int N> PCS_DEV DN<T, N> d_cbrt(const DN<T, N>& a) { T s = d_cbrt(a.v); return a.chain(s, s * d_recip(a.v) * (1.0 / 3.0)); }
 
 // =========================================================================================
+// D3<T>: value + 1st + 2nd + 3rd derivative along ONE direction (the critical-point solver: with T = DN<double,2>
+// seeded in (temperature, density) one evaluation gives p_rho, p_rhorho and their Jacobian, pure_critical.hpp)
+// =========================================================================================
+template <class T>
+struct D3 {
+    T v, d1, d2, d3;
+    PCS_DEV D3() {}
+    PCS_DEV D3(double x) : v(x), d1(0.0), d2(0.0), d3(0.0) {}
+    PCS_DEV D3(const T& a, const T& b, const T& c, const T& d) : v(a), d1(b), d2(c), d3(d) {}
+    // f(g): (f0, f1 g', f2 g'^2 + f1 g'', f3 g'^3 + 3 f2 g' g'' + f1 g''')
+    PCS_DEV D3 chain(const T& f0, const T& f1, const T& f2, const T& f3) const {
+        const T g1sq = d1 * d1;
+        return D3(f0, f1 * d1, f2 * g1sq + f1 * d2, f3 * (g1sq * d1) + 3.0 * (f2 * (d1 * d2)) + f1 * d3);
+    }
+};
+template <class T> struct is_dual<D3<T>> { static constexpr bool value = true; };
+template <class T> PCS_DEV double re(const D3<T>& a) { return re(a.v); }
+template <class T> PCS_DEV D3<T> operator+(const D3<T>& a, const D3<T>& b) { return D3<T>(a.v + b.v, a.d1 + b.d1, a.d2 + b.d2, a.d3 + b.d3); }
+template <class T> PCS_DEV D3<T> operator-(const D3<T>& a, const D3<T>& b) { return D3<T>(a.v - b.v, a.d1 - b.d1, a.d2 - b.d2, a.d3 - b.d3); }
+template <class T> PCS_DEV D3<T> operator-(const D3<T>& a) { return D3<T>(-a.v, -a.d1, -a.d2, -a.d3); }
+template <class T> PCS_DEV D3<T> operator*(const D3<T>& a, const D3<T>& b) {
+    return D3<T>(a.v * b.v, a.d1 * b.v + a.v * b.d1, a.d2 * b.v + 2.0 * (a.d1 * b.d1) + a.v * b.d2,
+                 a.d3 * b.v + 3.0 * (a.d2 * b.d1 + a.d1 * b.d2) + a.v * b.d3);
+}
+template <class T> PCS_DEV D3<T> operator+(const D3<T>& a, double b) { return D3<T>(a.v + b, a.d1, a.d2, a.d3); }
+template <class T> PCS_DEV D3<T> operator+(double b, const D3<T>& a) { return D3<T>(a.v + b, a.d1, a.d2, a.d3); }
+template <class T> PCS_DEV D3<T> operator-(const D3<T>& a, double b) { return D3<T>(a.v - b, a.d1, a.d2, a.d3); }
+template <class T> PCS_DEV D3<T> operator-(double b, const D3<T>& a) { return D3<T>(b - a.v, -a.d1, -a.d2, -a.d3); }
+template <class T> PCS_DEV D3<T> operator*(const D3<T>& a, double b) { return D3<T>(a.v * b, a.d1 * b, a.d2 * b, a.d3 * b); }
+template <class T> PCS_DEV D3<T> operator*(double b, const D3<T>& a) { return D3<T>(a.v * b, a.d1 * b, a.d2 * b, a.d3 * b); }
+template <class T> PCS_DEV D3<T> d_recip(const D3<T>& a) {
+    T r = d_recip(a.v);
+    T r2 = r * r;
+    return a.chain(r, -r2, 2.0 * (r2 * r), -6.0 * (r2 * r2));
+}
+template <class T> PCS_DEV D3<T> operator/(const D3<T>& a, const D3<T>& b) { return a * d_recip(b); }
+template <class T> PCS_DEV D3<T> operator/(const D3<T>& a, double b) { double r = 1.0 / b; return a * r; }
+template <class T> PCS_DEV D3<T> operator/(double b, const D3<T>& a) { return d_recip(a) * b; }
+template <class T> PCS_DEV D3<T> d_log(const D3<T>& a) { T r = d_recip(a.v); T r2 = r * r; return a.chain(d_log(a.v), r, -r2, 2.0 * (r2 * r)); }
+template <class T> PCS_DEV D3<T> d_exp(const D3<T>& a) { T e = d_exp(a.v); return a.chain(e, e, e, e); }
+template <class T> PCS_DEV D3<T> d_sqrt(const D3<T>& a) {
+    T s = d_sqrt(a.v);
+    T h = 0.5 * d_recip(s);  // 1/(2 sqrt x)
+    T rx = d_recip(a.v);
+    T f2 = -(h * rx) * 0.5;  // -1/(4 x sqrt x)
+    return a.chain(s, h, f2, -1.5 * (f2 * rx));  // f''' = 3/(8 x^2 sqrt x)
+}
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator*(const D3<T>& a, const T& b) { return D3<T>(a.v * b, a.d1 * b, a.d2 * b, a.d3 * b); }
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator*(const T& b, const D3<T>& a) { return D3<T>(a.v * b, a.d1 * b, a.d2 * b, a.d3 * b); }
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator+(const D3<T>& a, const T& b) { return D3<T>(a.v + b, a.d1, a.d2, a.d3); }
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator+(const T& b, const D3<T>& a) { return D3<T>(a.v + b, a.d1, a.d2, a.d3); }
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator-(const D3<T>& a, const T& b) { return D3<T>(a.v - b, a.d1, a.d2, a.d3); }
+template <class T, PCS_IFDUAL(T)> PCS_DEV D3<T> operator-(const T& b, const D3<T>& a) { return D3<T>(b - a.v, -a.d1, -a.d2, -a.d3); }
+
+// =========================================================================================
 // T2<T>: second-order Taylor coefficients in TWO variables (the partial densities rho_1, rho_2):
 //        v, g[2] = d/drho_i, h[3] = d2/drho_1^2, d2/drho_1 drho_2, d2/drho_2^2.
 // Carries everything the bubble/dew Newton needs (chemical potentials, pressure and their full
@@ -399,6 +455,10 @@ template <class T, int N> struct Lift<T2<DN<T, N>>, DN<T, N>> {
 };
 template <class T, int N> struct Lift<D2<DN<T, N>>, DN<T, N>> {
     static PCS_DEV D2<DN<T, N>> go(const DN<T, N>& p) { const DN<T, N> z(0.0); return D2<DN<T, N>>(p, z, z); }
+};
+template <class T> struct Lift<D3<T>, double> { static PCS_DEV D3<T> go(double p) { return D3<T>(p); } };
+template <class T, int N> struct Lift<D3<DN<T, N>>, DN<T, N>> {
+    static PCS_DEV D3<DN<T, N>> go(const DN<T, N>& p) { const DN<T, N> z(0.0); return D3<DN<T, N>>(p, z, z, z); }
 };
 
 }  // namespace pcs

@@ -1,0 +1,124 @@
+// Critical points of pure-component parameter rows and their parameter gradients (see include/pcsaft_hip.h:
+// pcs_pure_critical_point, pcs_pure_critical_point_vjp; solver and formulas in pure_critical.hpp).  Own translation unit,
+// compiled with strict IEEE semantics like pure_robust.hip: the bracketing of the critical temperature and the failure
+// detection rely on IEEE comparisons (feos_torch_amd/build.py).
+//
+// Launch shape as the other pure kernels: one row per lane, 256-thread workgroups, the [n,8] parameter rows of a workgroup
+// fetched with 16-byte loads and staged through LDS (72-byte padded rows); T_c, p_c, rho_c, status and the cotangents are SoA.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/pcsaft_hip.h"
+#include "abi_common.hpp"
+#include "pure_critical.hpp"
+
+using namespace pcs;
+using namespace pcs_abi;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int ROW_PAD = 9;
+
+// rows past n are clamped to row n-1 (their results are never stored)
+__device__ __forceinline__ void stage_rows(const double* __restrict__ params, int64_t n, int64_t row0, double* lds) {
+    const int t = threadIdx.x;
+    const double2* src = reinterpret_cast<const double2*>(params);
+    const int64_t last2 = n * 4 - 1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int idx2 = t + k * BLOCK;
+        int64_t g = row0 * 4 + idx2;
+        if (g > last2) g = last2 - 3 + (idx2 & 3);
+        const double2 v = src[g];
+        const int r = idx2 >> 2, c2 = idx2 & 3;
+        lds[r * ROW_PAD + 2 * c2] = v.x;
+        lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BLOCK) void k_pure_critical(const double* __restrict__ params, const double* __restrict__ t_init,
+                                                         int64_t n, double* __restrict__ tc, double* __restrict__ pc,
+                                                         double* __restrict__ rhoc, uint8_t* __restrict__ status,
+                                                         int32_t* __restrict__ iters) {
+    __shared__ double lds[BLOCK * ROW_PAD];
+    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
+    const int64_t i = row0 + threadIdx.x;
+    const bool live = i < n;
+    stage_rows(params, n, row0, lds);
+    double par[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) par[k] = lds[threadIdx.x * ROW_PAD + k];
+    const int64_t ii = live ? i : n - 1;
+    CritResult r;
+    const int st = critical_point(par, t_init ? t_init[ii] : 0.0, t_init != nullptr, r);  // wave-uniform call
+    if (!live) return;
+    const bool ok = st == 0;
+    if (tc) tc[i] = ok ? r.T : 0.0;
+    if (pc) pc[i] = ok ? r.p * r.T * P_UNIT : 0.0;
+    if (rhoc) rhoc[i] = ok ? r.rho * (1.0 / RHO_UNIT) : 0.0;
+    if (iters) iters[i] = ok ? r.iters : -1;
+    status[i] = ok ? 0 : 1;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_pure_critical_vjp(const double* __restrict__ params, const double* __restrict__ tc,
+                                                             const double* __restrict__ rhoc, int64_t n,
+                                                             const double* __restrict__ g_tc, const double* __restrict__ g_pc,
+                                                             const double* __restrict__ g_rhoc,
+                                                             double* __restrict__ grad_params) {
+    __shared__ double lds[BLOCK * ROW_PAD];
+    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
+    const int64_t i = row0 + threadIdx.x;
+    const bool live = i < n;
+    stage_rows(params, n, row0, lds);
+    double par[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) par[k] = lds[threadIdx.x * ROW_PAD + k];
+    const int64_t ii = live ? i : n - 1;
+    double g[8];
+    critical_point_vjp(par, tc[ii], rhoc[ii] * RHO_UNIT, g_tc ? g_tc[ii] : 0.0, g_pc ? g_pc[ii] : 0.0,
+                       g_rhoc ? g_rhoc[ii] : 0.0, g);
+    if (!live) return;
+    // a row that is not a converged critical point (T_c = rho_c = 0 from a failed solve) gives NaNs: the caller masks by status
+    double2* dst = reinterpret_cast<double2*>(grad_params + 8 * i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) dst[k] = make_double2(g[2 * k], g[2 * k + 1]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pcs_pure_critical_point(const double* params, const double* t_init, int64_t n, double* tc, double* pc, double* rhoc,
+                            uint8_t* status, int32_t* iters, void* stream) {
+    g_err[0] = 0;
+    if (int e = check_n(n)) return e;
+    if (n == 0) return 0;
+    if (!params || !status) return fail_msg("pcs_pure_critical_point: null required pointer");
+    if ((reinterpret_cast<uintptr_t>(params) & 15) != 0) return fail_msg("pcs_pure_critical_point: params must be 16-byte aligned");
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_pure_critical, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, t_init, n, tc, pc, rhoc, status,
+                       iters);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("k_pure_critical launch", e);
+    return 0;
+}
+
+int pcs_pure_critical_point_vjp(const double* params, const double* tc, const double* rhoc, int64_t n, const double* g_tc,
+                                const double* g_pc, const double* g_rhoc, double* grad_params, void* stream) {
+    g_err[0] = 0;
+    if (int e = check_n(n)) return e;
+    if (n == 0) return 0;
+    if (!params || !tc || !rhoc || !grad_params) return fail_msg("pcs_pure_critical_point_vjp: null required pointer");
+    if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grad_params)) & 15) != 0)
+        return fail_msg("pcs_pure_critical_point_vjp: params and grad_params must be 16-byte aligned");
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_pure_critical_vjp, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, tc, rhoc, n, g_tc, g_pc,
+                       g_rhoc, grad_params);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("k_pure_critical_vjp launch", e);
+    return 0;
+}
+
+}  // extern "C"

@@ -444,8 +444,8 @@ int launch_pure_liquid_density(const double* params, const double* temp, const d
 #if PCS_PURE_PART == 1
 extern "C" {
 
-int pcs_abi_version(void) { return 105; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
-                                            // 105: pcs_mix_stability, pcs_gc_stability
+int pcs_abi_version(void) { return 106; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+                                            // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp)
 
 const char* pcs_last_error(void) { return g_err; }
 

@@ -288,6 +288,47 @@ def pure_jacobian_vjp(which, params, temperature, pressure, rho_vl, gout, need=(
     return gp, gt, gpr
 
 
+def pure_critical_point(params, initial_temperature=None, want_iters=False):
+    """Critical point of every parameter row (pcs_pure_critical_point).
+    -> dict(t_c [K], p_c [Pa], rho_c [kmol/m3], status bool (True = failed), iters int32 or None)."""
+    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    params = _prep(params, device, (8,))
+    t_init = None if initial_temperature is None else _prep(initial_temperature, device)
+    n = params.shape[0]
+    _same_rows(n, initial_temperature=t_init)
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        tc = torch.empty(n, dtype=_F64, device=device)
+        pc = torch.empty(n, dtype=_F64, device=device)
+        rhoc = torch.empty(n, dtype=_F64, device=device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+        rc = L.pcs_pure_critical_point(_lib.ptr(params), _lib.ptr(t_init), n, _lib.ptr(tc), _lib.ptr(pc), _lib.ptr(rhoc),
+                                       _lib.ptr(status), _lib.ptr(iters), _lib.current_stream_ptr(device))
+        _lib.check(rc, "pcs_pure_critical_point")
+    return {"t_c": tc, "p_c": pc, "rho_c": rhoc, "status": status.view(torch.bool), "iters": iters}
+
+
+def pure_critical_point_vjp(params, t_c, rho_c, g_tc=None, g_pc=None, g_rhoc=None):
+    """Backward pass of pure_critical_point on converged rows: grad_params [n,8] (pcs_pure_critical_point_vjp)."""
+    device = t_c.device if isinstance(t_c, torch.Tensor) and t_c.is_cuda else _dev()
+    params = _prep(params, device, (8,))
+    t_c = _prep(t_c, device)
+    rho_c = _prep(rho_c, device)
+    g_tc = None if g_tc is None else _prep(g_tc, device)
+    g_pc = None if g_pc is None else _prep(g_pc, device)
+    g_rhoc = None if g_rhoc is None else _prep(g_rhoc, device)
+    n = t_c.shape[0]
+    _same_rows(n, parameters=params, rho_c=rho_c, g_tc=g_tc, g_pc=g_pc, g_rhoc=g_rhoc)
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        gp = torch.empty((n, 8), dtype=_F64, device=device)
+        rc = L.pcs_pure_critical_point_vjp(_lib.ptr(params), _lib.ptr(t_c), _lib.ptr(rho_c), n, _lib.ptr(g_tc), _lib.ptr(g_pc),
+                                           _lib.ptr(g_rhoc), _lib.ptr(gp), _lib.current_stream_ptr(device))
+        _lib.check(rc, "pcs_pure_critical_point_vjp")
+    return gp
+
+
 class PcSaft:
     """Mirror of the reference's Rust pyclass ``PcSaft`` (src/pcsaft.rs:13-80): static methods,
     float64 numpy arrays in, ``(rho, status)`` numpy arrays out, failed rows dropped from ``rho``."""

@@ -127,6 +127,48 @@ class _PureDerivatives(torch.autograd.Function):
                 grho.to(ctx.in_devices[2]) if need[2] else None)
 
 
+class _PureCritical(torch.autograd.Function):
+    """t_c[n_ok], p_c[n_ok], rho_c[n_ok], nans[n] = critical_point(parameters[n,8], initial temperature[n] or None)
+
+    One solve, one compaction plan (its 4-byte count is the call's only host synchronisation); the backward pass is the
+    implicit-function kernel on the converged rows (pcs_pure_critical_point_vjp), dropped rows receive zero gradient."""
+
+    @staticmethod
+    def forward(ctx, parameters, initial_temperature, box):
+        out_device = parameters.device
+        dev = native._dev() if not parameters.is_cuda else parameters.device
+        par = native._prep(parameters, dev, (8,))
+        t0 = None if initial_temperature is None else native._prep(initial_temperature, dev)
+        r = native.pure_critical_point(par, t0)
+        nans = r["status"]
+        comp = native.Compaction(nans)
+        box.append(comp)
+        tc, pc, rhoc = comp.gather(r["t_c"]), comp.gather(r["p_c"]), comp.gather(r["rho_c"])
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(comp.gather(par), tc, rhoc)
+            ctx.comp = comp
+        ctx.set_materialize_grads(False)
+        ctx.in_device = parameters.device
+        nans = nans.to(out_device)
+        ctx.mark_non_differentiable(nans)
+        return tc.to(out_device), pc.to(out_device), rhoc.to(out_device), nans
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_tc, g_pc, g_rhoc, _g_nans):
+        if g_tc is None and g_pc is None and g_rhoc is None:
+            return None, None, None
+        par, tc, rhoc = ctx.saved_tensors
+        comp = ctx.comp
+        if comp.n_ok == 0:
+            return torch.zeros((comp.n, 8), dtype=torch.float64, device=ctx.in_device), None, None
+        on = lambda g: None if g is None else g.to(comp.device).contiguous()
+        gp = native.pure_critical_point_vjp(par, tc, rhoc, on(g_tc), on(g_pc), on(g_rhoc))
+        if not comp.all_ok:
+            gp = comp.expand(gp)
+        return gp.to(ctx.in_device), None, None
+
+
 class PcSaftPure:
     def __init__(self, parameters):
         """parameters: [N, 8] float64 — m, sigma, epsilon_k, mu, kappa_ab, epsilon_k_ab, na, nb
@@ -186,6 +228,17 @@ class PcSaftPure:
     def equilibrium_liquid_density(self, temperature):
         """(nans, saturated liquid density [kmol/m3]) at T [K] (:217-233)."""
         return self._property("equilibrium_liquid_density", temperature, None)
+
+    def critical_point(self, initial_temperature=None):
+        """(nans, T_c [K], p_c [Pa], rho_c [kmol/m3]): the vapour-liquid critical point of every row (the end of the region in
+        which `vapor_pressure` has an answer), values for the converged rows only, differentiable w.r.t. the parameters.
+        initial_temperature [N] (optional): where the search for T_c starts.  Not part of the reference's class."""
+        if initial_temperature is not None:
+            initial_temperature = torch.as_tensor(initial_temperature, dtype=torch.float64)
+        box = []
+        t_c, p_c, rho_c, nans = _PureCritical.apply(self._par, initial_temperature, box)
+        self._reduce(box[0])
+        return nans, t_c, p_c, rho_c
 
     def _reduce(self, comp):
         if not comp.all_ok:

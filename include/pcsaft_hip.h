@@ -133,6 +133,37 @@ int pcs_pure_jacobian_vjp(int which, const double* params, const double* temp, c
                           void* stream);
 
 /*
+ * Vapour-liquid critical point of every parameter row: the state (T_c, rho_c) with
+ *     p_rho / kT = 1 + rho a'' = 0,   p_rhorho / kT = a'' + rho a''' = 0,   p_rhorhorho > 0
+ * (a: reduced residual Helmholtz energy density, p / kT = rho - a + rho a') and p_c = p(T_c, rho_c).  Where the equation of
+ * state has more than one such point (strongly polar rows: a second loop at liquid-like densities, at low temperatures), the
+ * one with the highest temperature is returned -- the end of the vapour-liquid region: above it the isotherms are
+ * mechanically stable at every density, below it pcs_pure_vle finds an equilibrium.  The reference has no counterpart (the
+ * engine it wraps offers a critical-point solve that its Python layer does not expose).
+ *   params  [n,8]  in   (16-byte aligned)
+ *   t_init  [n]    in   K, optional: temperature the bracketing of T_c starts from instead of 0.95 * 1.28 eps m^0.45
+ *   tc      [n]    out  K        (optional)
+ *   pc      [n]    out  Pa       (optional)
+ *   rhoc    [n]    out  kmol/m3  (optional)
+ *   status  [n]    out  uint8, 1 = failed (non-finite / non-physical parameters, iteration cap, iterate outside
+ *                       T > 0, 0 < eta < 0.7, or p_rhorhorho <= 0 at the converged point); outputs of such rows are 0
+ *   iters   [n]    out  int32 Newton iterations, -1 for failed rows (optional, diagnostics)
+ * One kernel, no workspace.
+ */
+int pcs_pure_critical_point(const double* params, const double* t_init, int64_t n, double* tc, double* pc, double* rhoc,
+                            uint8_t* status, int32_t* iters, void* stream);
+
+/*
+ * Backward pass of pcs_pure_critical_point at converged rows, by the implicit-function theorem
+ * (d(T_c, rho_c)/dtheta = -J^-1 dF/dtheta with F = (p_rho, p_rhorho), dp_c/dtheta = p_theta + p_T dT_c/dtheta):
+ *   grad_params[i,k] = g_tc[i] dT_c/dtheta_k + g_pc[i] dp_c/dtheta_k + g_rhoc[i] drho_c/dtheta_k.
+ *   tc [n] K, rhoc [n] kmol/m3 in: outputs of pcs_pure_critical_point (rows with status 1 give NaN rows: mask them);
+ *   g_tc, g_pc, g_rhoc [n] in, each optional (NULL = zero cotangent); grad_params [n,8] out (16-byte aligned).
+ */
+int pcs_pure_critical_point_vjp(const double* params, const double* tc, const double* rhoc, int64_t n, const double* g_tc,
+                                const double* g_pc, const double* g_rhoc, double* grad_params, void* stream);
+
+/*
  * Binary-mixture bubble point (dew = 0: z = liquid mole fraction of component 1) or dew point
  * (dew = 1: z = vapour mole fraction of component 1) at fixed temperature.
  * Replaces PcSaft.bubble_point / PcSaft.dew_point(parameters[N,2,8], kij[N,2], temperature[N],

@@ -6,6 +6,7 @@ with HIP events on the launch stream, inputs resident in HBM.
   config 5: GcPcSaftMix bubble / dew point, batch 1e6
   stability: tangent-plane stability analysis (pcs_mix_stability / pcs_gc_stability) of the converged bubble and dew
              feeds of configs 4 and 5 (the specified phase at the solution), batch 1e6 minus the failed rows
+  critical: PcSaftPure.critical_point kernels, batch 1e6 and 1e7 (forward, forward + backward, vapor_pressure alongside)
 Prints one JSON object per config."""
 import json
 import os
@@ -109,3 +110,25 @@ if "stability" in which:
         cnt = torch.bincount(r["status"].long(), minlength=4).tolist()
         print(json.dumps({"config": f"GcPcSaftMix stability of the {'dew' if dew else 'bubble'} feeds batch={len(ok)}", "ms": ms,
                           "rows_per_s": len(ok) / ms * 1e3, "status_counts": cnt, "flagged_fraction": 1.0 - cnt[0] / len(ok)}))
+if "critical" in which:
+    # critical points of the pure_batch parameter rows: forward (pcs_pure_critical_point) and forward + backward
+    # (+ pcs_pure_critical_point_vjp with all three cotangents), next to vapor_pressure from the same process
+    for n in (1_000_000, 10_000_000):
+        P, T = pure_batch(n)
+        Pd, Td = d(P), d(T)
+        g = [torch.ones(n, dtype=torch.float64, device="cuda") for _ in range(3)]
+        ms_vp, _ = timed(lambda: native.pure_vapor_pressure(Pd, Td))
+        ms, r = timed(lambda: native.pure_critical_point(Pd, want_iters=True), reps=3)
+
+        def fwd_bwd():
+            r = native.pure_critical_point(Pd)
+            return native.pure_critical_point_vjp(Pd, r["t_c"], r["rho_c"], *g)
+
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        failed = r["status"]
+        polar, assoc = Pd[:, 3] != 0, Pd[:, 4] != 0
+        by_class = {name: int((failed & (polar == a) & (assoc == b)).sum())
+                    for name, a, b in (("plain", False, False), ("polar", True, False), ("assoc", False, True), ("polar+assoc", True, True))}
+        it = torch.bincount(r["iters"][~failed].long()).tolist()
+        print(json.dumps({"config": f"PcSaftPure critical_point batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3, "ms_forward_backward": ms_fb,
+                          "ms_vapor_pressure": ms_vp, "failed": int(failed.sum()), "failed_by_class": by_class, "newton_iterations": it}))
