@@ -107,8 +107,9 @@ __device__ __forceinline__ int k1_bucket(const double* row) {
 // LITE (pressure-only output, fp32 pre-solve available): vle_fast_lite; rows without a usable fp32 result are
 // appended with bit 31 set (k_pure_vle_fallback takes them), rows for the robust pass without.
 // POLISH (with LITE): the densities are handed out (rho_eq / rho_vl) and take the exact Newton update of vle_lite_finish<true>
-template <bool LITE, bool POLISH = false>
-__global__ __launch_bounds__(BLOCK, LITE ? K1_WAVES_LITE : K1_WAVES) void k_pure_vle(const double* __restrict__ params,
+// RHO (with LITE, without POLISH; k_pure_vle_rho): rho_vl is handed out next to an unchanged p_sat (vle_polish_densities)
+template <bool LITE, bool POLISH, bool RHO>
+__device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
                                                     const double* __restrict__ temp, int64_t n,
                                                     double* __restrict__ p_sat, double* __restrict__ rho_eq,
                                                     double* __restrict__ rho_vl, uint8_t* __restrict__ status,
@@ -162,12 +163,13 @@ __global__ __launch_bounds__(BLOCK, LITE ? K1_WAVES_LITE : K1_WAVES) void k_pure
     const double T = lds[r * ROW_PAD + 8];
 
     VleResult res;
-    int st;  // wave-uniform calls
+    int st;  // every lane of the wave makes the call (its loops end on ballots over the lanes still working)
+    const bool polish_rho = rho_vl != nullptr;  // densities as an output of a solve that stops at the pressure tolerances
 #ifdef PCS_F32_PRESOLVE
-    if (LITE) st = vle_fast_lite<POLISH>(&lds[r * ROW_PAD], lds[r * ROW_PAD + 8], res);  // the row is re-read from LDS for the fp64 coefficients
-    else st = rho_eq ? vle_fast<true>(par, T, res, 1e-8, TOL_STEP) : vle_fast<true>(par, T, res);
+    if (LITE) st = vle_fast_lite<POLISH, RHO>(&lds[r * ROW_PAD], lds[r * ROW_PAD + 8], res);  // the row is re-read from LDS for the fp64 coefficients
+    else st = rho_eq ? vle_fast<true>(par, T, res, 1e-8, TOL_STEP) : vle_fast<true>(par, T, res, TOL_L_P, TOL_V_P, polish_rho);
 #else
-    st = rho_eq ? vle_fast<false>(par, T, res, 1e-8, TOL_STEP) : vle_fast<false>(par, T, res);
+    st = rho_eq ? vle_fast<false>(par, T, res, 1e-8, TOL_STEP) : vle_fast<false>(par, T, res, TOL_L_P, TOL_V_P, polish_rho);
 #endif
 
     if (!live) return;
@@ -187,6 +189,27 @@ __global__ __launch_bounds__(BLOCK, LITE ? K1_WAVES_LITE : K1_WAVES) void k_pure
         if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)((uint32_t)i | (st == ST_FALLBACK ? 0x80000000u : 0u));  // n < 2^31 checked on the host
     }
 }
+
+template <bool LITE, bool POLISH = false>
+__global__ __launch_bounds__(BLOCK, LITE ? K1_WAVES_LITE : K1_WAVES) void k_pure_vle(const double* __restrict__ params,
+                                                    const double* __restrict__ temp, int64_t n,
+                                                    double* __restrict__ p_sat, double* __restrict__ rho_eq,
+                                                    double* __restrict__ rho_vl, uint8_t* __restrict__ status,
+                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry) {
+    pure_vle_rows<LITE, POLISH, false>(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry);
+}
+
+#if PCS_PURE_PART == 1
+// the pressure-only kernel handing out rho_vl (pcs_pure_vapor_pressure with densities): p_sat and status bit for bit as
+// k_pure_vle<true, false>, the densities of the solved rows through vle_polish_densities
+__global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_rho(const double* __restrict__ params,
+                                                    const double* __restrict__ temp, int64_t n,
+                                                    double* __restrict__ p_sat, double* __restrict__ rho_eq,
+                                                    double* __restrict__ rho_vl, uint8_t* __restrict__ status,
+                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry) {
+    pure_vle_rows<true, false, true>(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry);
+}
+#endif
 
 // Rows of the list with bit 31 set (no usable fp32 pre-solve): the all-fp64 fast path.  Solved rows keep the
 // bit (the robust pass skips them), rows that need the robust pass get it cleared.
@@ -210,7 +233,7 @@ __global__ __launch_bounds__(64) void k_pure_vle_fallback(const double* __restri
         for (int j = 0; j < 8; j++) par[j] = params[8 * i + j];
         const double T = temp[i];
         VleResult res;
-        int st = rho_eq ? vle_fast<false>(par, T, res, 1e-8, TOL_STEP) : vle_fast<false>(par, T, res);
+        int st = rho_eq ? vle_fast<false>(par, T, res, 1e-8, TOL_STEP) : vle_fast<false>(par, T, res, TOL_L_P, TOL_V_P, rho_vl != nullptr);
         if (st == ST_OK) {
             if (p_sat) p_sat[i] = res.p_star * T * P_UNIT;
             if (rho_eq) rho_eq[i] = res.rho_l * (1.0 / RHO_UNIT);
@@ -460,15 +483,21 @@ static int launch_vle_fast(const double* params, const double* temp, int64_t n, 
     hipError_t e;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
     // main kernel (lean: rows without an fp32 pre-solve go to the list with bit 31 set) + all-fp64 fallback kernel.
-    //  * pressure only (and pcs_pure_vapor_pressure, whatever it hands out): k_pure_vle<true>, densities converged to ~1e-9
-    //    (enough for p*, whose error is of second order in them);
+    //  * pressure only: k_pure_vle<true>, densities converged to ~1e-9 inside the kernel (enough for p*, whose error is of
+    //    second order in them) and not handed out;
+    //  * pcs_pure_vapor_pressure with densities: k_pure_vle_rho, the same solve and the same p_sat bits + the exact Newton
+    //    update of vle_polish_densities on the densities it hands out (the fp32-slope iteration leaves rho_V up to 1.9e-6 off);
     //  * rho_vl without rho_eq (the Jacobian kernels' input), and everything under all_fp64 (pcs_pure_vle_fp64):
     //    k_pure_vle<false>, the fp64 D2 iteration from the fp32 pre-solve's start -- one iteration at the pressure
-    //    tolerances, densities ~1e-11 (0.945 ms per 1e7 rows against 0.990 for the next form);
+    //    tolerances, which leaves rho_V up to 5.9e-9 off, + vle_polish_densities when rho_vl is an output: 0.98 -> 1.35 ms
+    //    per 1e7 rows for the second D2 evaluation of both phases;
     //  * rho_eq requested (tolerance 1e-8 on the liquid step: two D2 iterations of the all-fp64 kernel, 1.55-1.67 ms): the
     //    pressure-only kernel + the exact Newton update of vle_lite_finish<true> instead, 1.22 ms (round 3).
     if (all_fp64 || (!rho_eq && rho_vl && !force_lite)) {
         if (int ef = launch_pure_vle_full(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, s)) return ef;
+    } else if (!rho_eq && rho_vl) {  // pcs_pure_vapor_pressure with densities: the same p_sat bits, rho_vl polished
+        hipLaunchKernelGGL(k_pure_vle_rho, dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status,
+                           iters, retry);
     } else if (!rho_eq) {
         hipLaunchKernelGGL((k_pure_vle<true, false>), dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status,
                            iters, retry);

@@ -191,6 +191,38 @@ PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv) {
     return vle_step(l, v, rl, rv, d_recip(l.dp), d_recip(v.dp));
 }
 
+// Densities handed out next to a pressure that stopped at the pressure tolerances (TOL_L_P / TOL_V_P, or the linear
+// iteration of vle_lite_finish): they are only as good as that last step squared, up to 6e-9 on ordinary rows and 2e-6
+// after the fp32-slope iteration (measured against the long-double oracle on the saturation-line grid).  Lanes with `on`
+// take exact Newton updates of the coupled iteration until the step is below 1e-7 (liquid) / 1e-6 (vapour), the
+// acceptance of vle_lite_finish<true>, at most three; the updated densities are converged to the square of that.  The
+// pressure is not touched: a call returns the same p_sat bits with and without the densities.  Never worse than before by
+// construction: a lane whose step is not one to trust, that has not converged after the third update, or whose updated
+// densities no longer pass the acceptance of the solve (0 < rho_V < 0.7 rho_L) keeps the densities the solve left.
+PCS_DEV void vle_polish_densities(const PureCoef<double>& c, bool on, double& rl_io, double& rv_io) {
+    double rl = rl_io, rv = rv_io;
+    bool conv = !on, keep = on;
+    for (int k = 0; k < 3; k++) {
+        if (!conv) {
+            const Eval l = pure_eval(c, rl), v = pure_eval(c, rv);
+            const VleStep s = vle_step(l, v, rl, rv);
+            if (is_finite_bits(s.dl) && is_finite_bits(s.dv) && fabs(s.dl) < 0.1 * rl && fabs(s.dv) < 0.5 * rv) {
+                conv = (fabs(s.dl) <= 1e-7 * rl) && (fabs(s.dv) <= 1e-6 * rv);
+                rl += s.dl;
+                rv += s.dv;
+            } else {
+                conv = true;  // not a Newton step to trust
+                keep = false;
+            }
+        }
+        if (__ballot(!conv) == 0ull) break;
+    }
+    if (keep && conv && rv > 0.0 && rv < 0.7 * rl) {
+        rl_io = rl;
+        rv_io = rv;
+    }
+}
+
 // Fast path of the pure VLE: zero-pressure liquid + ideal-gas vapour initialisation, then the
 // coupled Newton.  ST_RETRY = this initialisation does not apply (near-critical temperature);
 // the robust kernel takes those rows.
@@ -199,8 +231,10 @@ PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv) {
 // caller passes a tighter value when that output is requested.
 // LEAN: lanes without a usable fp32 pre-solve are not solved here (ST_FALLBACK, see vle_fast_lite): the main
 // kernels instantiate this, k_pure_vle_fallback the complete form.
+// polish_rho (wave-uniform): the densities are an output and the tolerances are the pressure's -> vle_polish_densities.
 template <bool LEAN>
-PCS_DEV int vle_fast(const double* par, double T, VleResult& out, double tol_l = TOL_L_P, double tol_v = TOL_V_P) {
+PCS_DEV int vle_fast(const double* par, double T, VleResult& out, double tol_l = TOL_L_P, double tol_v = TOL_V_P,
+                     bool polish_rho = false) {
     double rl = 0.0, rv = 0.0;
     Eval l;
     bool warm = false;
@@ -259,8 +293,9 @@ PCS_DEV int vle_fast(const double* par, double T, VleResult& out, double tol_l =
         if (active && !done) l = pure_eval(c, rl);
     }
     if (LEAN && !warm) return ST_FALLBACK;
-    if (done && out.rho_v < 0.7 * out.rho_l && vapour_is_physical(out.p_star, out.rho_v)) return ST_OK;
-    return ST_RETRY;  // includes cap hit and near-critical states: let the robust path decide
+    const bool ok = done && out.rho_v < 0.7 * out.rho_l && vapour_is_physical(out.p_star, out.rho_v);
+    if (polish_rho) vle_polish_densities(c, ok, out.rho_l, out.rho_v);
+    return ok ? ST_OK : ST_RETRY;  // ST_RETRY includes cap hit and near-critical states: let the robust path decide
 }
 
 #ifdef PCS_F32_PRESOLVE
@@ -274,7 +309,9 @@ PCS_DEV int vle_fast(const double* par, double T, VleResult& out, double tol_l =
 // POLISH (densities requested: equilibrium_liquid_density, rho_vl for the Jacobians): one more update of both densities
 // with the exact dp/drho of an fp64 D2 evaluation at the converged state -- the iteration above leaves them at ~1e-9
 // (linear convergence with the fp32 slope), the exact Newton step squares that.  p* then carries the exact second-order term.
-template <bool POLISH = false>
+// RHO (without POLISH: pcs_pure_vapor_pressure handing out rho_vl): status and p* exactly as without it, the densities of
+// the solved lanes through vle_polish_densities.
+template <bool POLISH = false, bool RHO = false>
 PCS_DEV int vle_lite_finish(const double* par, double T, bool warm, double rl, double rv, float dpl32, float dpv32,
                             VleResult& out, double tol_l = TOL_L_P, double tol_v = TOL_V_P) {
     PureCoef<double> c;
@@ -335,18 +372,19 @@ PCS_DEV int vle_lite_finish(const double* par, double T, bool warm, double rl, d
             out.iters++;
         }
     }
-    if (done && out.rho_v < 0.7 * out.rho_l && vapour_is_physical(out.p_star, out.rho_v)) return ST_OK;
-    return ST_RETRY;
+    const bool ok = done && out.rho_v < 0.7 * out.rho_l && vapour_is_physical(out.p_star, out.rho_v);
+    if (RHO && !POLISH) vle_polish_densities(c, ok, out.rho_l, out.rho_v);
+    return ok ? ST_OK : ST_RETRY;
 }
 
-template <bool POLISH = false>
+template <bool POLISH = false, bool RHO = false>
 PCS_DEV int vle_fast_lite(const double* par, double T, VleResult& out, double tol_l = TOL_L_P, double tol_v = TOL_V_P) {
     double rl = 0.0, rv = 0.0;
     float dpl32 = 1.0f, dpv32 = 1.0f;
     PureCoefF cf;
     pure_coef_f32(cf, par, T);
     const bool warm = vle_presolve_f32(cf, rl, rv, dpl32, dpv32);
-    return vle_lite_finish<POLISH>(par, T, warm, rl, rv, dpl32, dpv32, out, tol_l, tol_v);
+    return vle_lite_finish<POLISH, RHO>(par, T, warm, rl, rv, dpl32, dpv32, out, tol_l, tol_v);
 }
 #endif
 

@@ -232,6 +232,7 @@ class PcSaftPure:
     def critical_point(self, initial_temperature=None):
         """(nans, T_c [K], p_c [Pa], rho_c [kmol/m3]): the vapour-liquid critical point of every row (the end of the region in
         which `vapor_pressure` has an answer), values for the converged rows only, differentiable w.r.t. the parameters.
+        `vapor_pressure` answers on every row up to 0.999 T_c and on a shrinking share above.
         initial_temperature [N] (optional): where the search for T_c starts.  Not part of the reference's class."""
         if initial_temperature is not None:
             initial_temperature = torch.as_tensor(initial_temperature, dtype=torch.float64)

@@ -118,6 +118,8 @@ def test_kernel_stack_frames_and_occupancy(hip_lib):
     assert len(lite) == 1 and lite[0]["scratch"] == 0 and lite[0]["occupancy"] >= 4, lite
     polish = [r for name, r in res.items() if "k_pure_vle<true, true>" in name]  # + the exact Newton update of the densities
     assert len(polish) == 1 and polish[0]["scratch"] <= 192 and polish[0]["occupancy"] >= 4, polish
+    rho = res["k_pure_vle_rho"]  # the pressure-only kernel handing out polished densities (pcs_pure_vapor_pressure)
+    assert rho["scratch"] <= 192 and rho["occupancy"] >= 4, rho
     for which in range(3):
         jac = res[f"void k_pure_jacobian<{which}>"]
         assert jac["occupancy"] >= 2 and jac["scratch"] <= 256, (which, jac)
