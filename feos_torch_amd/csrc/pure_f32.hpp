@@ -18,6 +18,20 @@ constexpr float PCS_F32_PREDICT_TOL_L = 5e-6f;
 constexpr float PCS_F32_PREDICT_TOL_V = 5e-5f;
 constexpr float PCS_F32_PREDICT_CMAX = 1e3f;
 constexpr int PCS_F32_DENSE_LEVELS = 3;  // restarts of the fp32 liquid root on the dense side (1 = eta 0.58 only)
+// Lean coupled iterations (a and a' only; dp/drho carried and updated from the pressures in hand: carry_slope,
+// presolve_coupled):
+// LEAN_MAX:   largest relative vapour step after which the next vapour evaluation may be lean: every ordinary step (a step
+//             taken in ln(rho) always forces the full form).  It does not bound the error of the slope handed to the fp64
+//             finish.  That slope comes from the lane's last update: trapezoid across a step d, error p''' d^2 / 12 -- small
+//             for the near-quadratic p(rho) of a vapour even at a large d -- or three-point, ~ p''' d0 d1 / 6.  No a-priori
+//             bound is claimed for it; it was measured instead: the CPU restatement of the iteration puts it at 1.2e-3 at
+//             most (median 3e-5), and p_sat against the long-double oracle on 1e6 rows is no worse than with the
+//             exact slopes of the full evaluation.
+// SECANT_MIN: the pressure carries ~1e-7 rho (1 + |a'|) of fp32 rounding noise, the quotient is taken over step * rho and
+//             doubled by the trapezoid: its relative error is ~2e-7 (1 + |a'|) / (step p').  Updated only when that is
+//             below ~1e-3, i.e. step * p' >= 3e-4 (1 + |a'|); below it the kept slope is off by less than that anyway.
+constexpr float PCS_F32_LEAN_MAX = 0.5f;
+constexpr float PCS_F32_SECANT_MIN = 3e-4f;
 constexpr float PCS_F32_LIQ_TOL = 1e-1f;  // relative (scaled-Newton) step at which the fp32 liquid initialiser hands over to the coupled iteration
 
 struct F2 {  // value, d/drho, d2/drho2 in fp32
@@ -61,6 +75,28 @@ PCS_DEV F2 hornerf(const float* coef, F2 x) {  // x.d2 == 0 (x = eta = ceta * rh
         p = fmaf(p, x.v, coef[i]);
     }
     return f2(p, d1 * x.d1, 2.0f * d2 * (x.d1 * x.d1));
+}
+
+struct F1 {  // value, d/drho in fp32: the dipole arithmetic of the evaluation without a''
+    float v, d1;
+};
+PCS_DEV F1 f1(float v, float d1) { F1 r; r.v = v; r.d1 = d1; return r; }
+PCS_DEV F1 operator-(F1 a, F1 b) { return f1(a.v - b.v, a.d1 - b.d1); }
+PCS_DEV F1 operator*(F1 a, float b) { return f1(a.v * b, a.d1 * b); }
+PCS_DEV F1 operator*(F1 a, F1 b) { return f1(a.v * b.v, fmaf(a.d1, b.v, a.v * b.d1)); }
+PCS_DEV F1 recipf(F1 a) {
+    float r = __builtin_amdgcn_rcpf(a.v);
+    return f1(r, -(r * r) * a.d1);
+}
+template <int N>
+PCS_DEV F1 hornerf(const float* coef, F1 x) {
+    float p = coef[N - 1], d1 = 0.0f;
+#pragma unroll
+    for (int i = N - 2; i >= 0; i--) {
+        d1 = fmaf(d1, x.v, p);
+        p = fmaf(p, x.v, coef[i]);
+    }
+    return f1(p, d1 * x.d1);
 }
 
 struct PureCoefF {
@@ -143,47 +179,59 @@ struct EvalF { float a, p, dp, mu; };
 // value/d1/d2 arithmetic: HS' = (4-2eta)u^3, HS'' = (10-4eta)u^4, (ln g)' = 3u - w, (ln g)'' = 3u^2 - w^2,
 // A' = (8+20eta-4eta^2)u^5, A'' = (60+72eta-12eta^2)u^6, and with q = u^2 w^2, s = u + w:
 // B' = q (poly' + 2 poly s), B'' = 2 q s (poly' + 2 poly s) + q (poly'' + 2 poly' s + 2 poly (u^2 + w^2)).
-template <int N>
+// D2 = false everywhere below: value and first derivative only (two-term recurrences, no a''), the form of the lean
+// coupled iterations; mirrors the D1s specialisation of pure_a (pure_model.hpp).
+template <int N, bool D2>
 PCS_DEV void horner3f(const float* coef, float x, float& p, float& d1, float& d2) {  // p, p', p''
     p = coef[N - 1];
     d1 = 0.0f;
     float h = 0.0f;
 #pragma unroll
     for (int i = N - 2; i >= 0; i--) {
-        h = fmaf(h, x, d1);
+        if (D2) h = fmaf(h, x, d1);
         d1 = fmaf(d1, x, p);
         p = fmaf(p, x, coef[i]);
     }
     d2 = 2.0f * h;
 }
+template <bool D2>
 PCS_DEV F2 core_closed_f32(const PureCoefF& c, float rho) {
     const float eta = rho * c.ceta;
     const float u = __builtin_amdgcn_rcpf(1.0f - eta), w = __builtin_amdgcn_rcpf(2.0f - eta);
     const float u2 = u * u, u3 = u2 * u, u4 = u2 * u2, w2 = w * w;
-    const float HS = eta * (4.0f - 3.0f * eta) * u2, HS1 = (4.0f - 2.0f * eta) * u3, HS2 = (10.0f - 4.0f * eta) * u4;
-    const float LG = f_log((1.0f - 0.5f * eta) * u3), LG1 = 3.0f * u - w, LG2 = 3.0f * u2 - w2;
-    const float F = c.m * HS - c.mm1 * LG, F1 = c.m * HS1 - c.mm1 * LG1, F2_ = c.m * HS2 - c.mm1 * LG2;
+    const float HS = eta * (4.0f - 3.0f * eta) * u2, HS1 = (4.0f - 2.0f * eta) * u3;
+    const float LG = f_log((1.0f - 0.5f * eta) * u3), LG1 = 3.0f * u - w;
+    const float F = c.m * HS - c.mm1 * LG, F1_ = c.m * HS1 - c.mm1 * LG1;
     float I1, I1a, I1b, I2, I2a, I2b;
-    horner3f<7>(c.ai, eta, I1, I1a, I1b);
-    horner3f<7>(c.bi, eta, I2, I2a, I2b);
-    const float A = eta * (8.0f - 2.0f * eta) * u4, A1 = (8.0f + eta * (20.0f - 4.0f * eta)) * (u4 * u),
-                A2 = (60.0f + eta * (72.0f - 12.0f * eta)) * (u4 * u2);
+    horner3f<7, D2>(c.ai, eta, I1, I1a, I1b);
+    horner3f<7, D2>(c.bi, eta, I2, I2a, I2b);
+    const float A = eta * (8.0f - 2.0f * eta) * u4, A1 = (8.0f + eta * (20.0f - 4.0f * eta)) * (u4 * u);
     const float poly = eta * (20.0f + eta * (-27.0f + eta * (12.0f - 2.0f * eta)));
-    const float poly1 = 20.0f + eta * (-54.0f + eta * (36.0f - 8.0f * eta)), poly2 = -54.0f + eta * (72.0f - 24.0f * eta);
+    const float poly1 = 20.0f + eta * (-54.0f + eta * (36.0f - 8.0f * eta));
     const float q = u2 * w2, s = u + w;
     const float t = poly1 + 2.0f * poly * s;
-    const float B = poly * q, B1 = q * t, B2 = q * (2.0f * s * t + poly2 + 2.0f * poly1 * s + 2.0f * poly * (u2 + w2));
-    const float D = 1.0f + c.m * A - c.mm1 * B, D1 = c.m * A1 - c.mm1 * B1, D2 = c.m * A2 - c.mm1 * B2;
+    const float B = poly * q, B1 = q * t;
+    const float D = 1.0f + c.m * A - c.mm1 * B, D1 = c.m * A1 - c.mm1 * B1;
     const float C = __builtin_amdgcn_rcpf(D), Csq = C * C;
-    const float C1 = -D1 * Csq, C2 = (2.0f * D1 * D1 * C - D2) * Csq;
+    const float C1 = -D1 * Csq;
     const float G = c.kd1 * I1 + c.kd2 * (C * I2);
     const float G1 = c.kd1 * I1a + c.kd2 * (C1 * I2 + C * I2a);
-    const float G2 = c.kd1 * I1b + c.kd2 * (C2 * I2 + 2.0f * C1 * I2a + C * I2b);
     const float ce = c.ceta, rc = rho * ce;  // eta-derivatives -> rho-derivatives
     F2 a;
     a.v = rho * (F + rho * G);
-    a.d1 = F + rc * F1 + rho * (2.0f * G + rc * G1);
-    a.d2 = ce * (2.0f * F1 + rc * F2_) + 2.0f * G + rc * (4.0f * G1 + rc * G2);
+    a.d1 = F + rc * F1_ + rho * (2.0f * G + rc * G1);
+    a.d2 = 0.0f;
+    if (D2) {
+        const float HS2 = (10.0f - 4.0f * eta) * u4, LG2 = 3.0f * u2 - w2;
+        const float F2_ = c.m * HS2 - c.mm1 * LG2;
+        const float A2 = (60.0f + eta * (72.0f - 12.0f * eta)) * (u4 * u2);
+        const float poly2 = -54.0f + eta * (72.0f - 24.0f * eta);
+        const float B2 = q * (2.0f * s * t + poly2 + 2.0f * poly1 * s + 2.0f * poly * (u2 + w2));
+        const float D2_ = c.m * A2 - c.mm1 * B2;
+        const float C2 = (2.0f * D1 * D1 * C - D2_) * Csq;
+        const float G2 = c.kd1 * I1b + c.kd2 * (C2 * I2 + 2.0f * C1 * I2a + C * I2b);
+        a.d2 = ce * (2.0f * F1_ + rc * F2_) + 2.0f * G + rc * (4.0f * G1 + rc * G2);
+    }
     return a;
 }
 
@@ -199,16 +247,15 @@ PCS_DEV F2 core_closed_f32(const PureCoefF& c, float rho) {
 //   h' = 2.5 u^2 + 4 eta u^3 + 1.5 eta^2 u^4,   h'' = 9 u^3 + 15 eta u^4 + 6 eta^2 u^5.
 // About a third of the generic value/d1/d2 arithmetic of the term (checked against it: tests/test_pure_gpu.py goldens and
 // the 1e6-row parity runs).  XA, XB themselves from the cancellation-free closed forms of pure_model.hpp.
+template <bool D2>
 PCS_DEV F2 assoc_closed_f32(const PureCoefF& c, float rho) {
     const float eta = rho * c.ceta;
     const float u = __builtin_amdgcn_rcpf(1.0f - eta);
     const float u2 = u * u, eu = eta * u;
     const float h = u * (1.0f + eu * (1.5f + 0.5f * eu));
     const float h1 = u2 * (2.5f + eu * (4.0f + 1.5f * eu));
-    const float h2 = u2 * u * (9.0f + eu * (15.0f + 6.0f * eu));
     const float S = rho * c.da * h;
     const float S1 = c.da * (h + eta * h1);
-    const float S2 = c.da * c.ceta * (2.0f * h1 + eta * h2);
     const float sa = c.na * S, sb = c.nb * S;  // rho_a Delta, rho_b Delta
     const float t = sb - sa;
     const float aux = 1.0f - t;
@@ -227,20 +274,25 @@ PCS_DEV F2 assoc_closed_f32(const PureCoefF& c, float rho) {
     const float q = c.na * (f_log(xa) - 0.5f * xa + 0.5f) + c.nb * (f_log(xb) - 0.5f * xb + 0.5f);
     const float nn = c.na * c.nb;
     const float q1 = -nn * xa * xb;
-    const float al = c.nb * xa * xa, be = c.na * xb * xb;
-    const float rden = __builtin_amdgcn_rcpf(1.0f - al * be * S * S);
-    const float xa1 = al * (be * S * xa - xb) * rden, xb1 = be * (al * S * xb - xa) * rden;
-    const float q2 = -nn * (xa1 * xb + xa * xb1);
     F2 r;
     r.v = rho * q;
     r.d1 = q + rho * q1 * S1;
-    r.d2 = 2.0f * q1 * S1 + rho * (q2 * S1 * S1 + q1 * S2);
+    r.d2 = 0.0f;
+    if (D2) {
+        const float h2 = u2 * u * (9.0f + eu * (15.0f + 6.0f * eu));
+        const float S2 = c.da * c.ceta * (2.0f * h1 + eta * h2);
+        const float al = c.nb * xa * xa, be = c.na * xb * xb;
+        const float rden = __builtin_amdgcn_rcpf(1.0f - al * be * S * S);
+        const float xa1 = al * (be * S * xa - xb) * rden, xb1 = be * (al * S * xb - xa) * rden;
+        const float q2 = -nn * (xa1 * xb + xa * xb1);
+        r.d2 = 2.0f * q1 * S1 + rho * (q2 * S1 * S1 + q1 * S2);
+    }
     return r;
 }
 
 // same model as pure_a() (pure_model.hpp), fp32
 PCS_DEV EvalF pure_eval_f32(const PureCoefF& c, float rho) {
-    F2 a = core_closed_f32(c, rho);
+    F2 a = core_closed_f32<true>(c, rho);
     if (c.polar || c.assoc) {
         F2 r = f2(rho, 1.0f, 0.0f);
         F2 eta = r * c.ceta;
@@ -251,7 +303,7 @@ PCS_DEV EvalF pure_eval_f32(const PureCoefF& c, float rho) {
             a = a + (rho2 * c.qm) * ((J1 * J1) * recipf(J1 - r * J2));
         }
         if (c.assoc) {
-            a = a + assoc_closed_f32(c, rho);
+            a = a + assoc_closed_f32<true>(c, rho);
         }
     }
     EvalF ec;
@@ -260,6 +312,34 @@ PCS_DEV EvalF pure_eval_f32(const PureCoefF& c, float rho) {
     ec.dp = 1.0f + rho * a.d2;
     ec.mu = a.d1;
     return ec;
+}
+
+// The same without a'': a, p and mu = a' (no dp/drho).  About two thirds of the arithmetic of pure_eval_f32.
+struct EvalF1 { float a, p, mu; };
+PCS_DEV EvalF1 pure_eval1_f32(const PureCoefF& c, float rho) {
+    const F2 core = core_closed_f32<false>(c, rho);
+    float a = core.v, a1 = core.d1;
+    if (c.polar || c.assoc) {
+        if (c.polar) {
+            const F1 r = f1(rho, 1.0f);
+            const F1 eta = r * c.ceta;
+            const F1 J1 = hornerf<5>(c.j1, eta);
+            const F1 J2 = hornerf<4>(c.j2, eta);
+            const F1 d = ((r * r) * c.qm) * ((J1 * J1) * recipf(J1 - r * J2));
+            a += d.v;
+            a1 += d.d1;
+        }
+        if (c.assoc) {
+            const F2 as = assoc_closed_f32<false>(c, rho);
+            a += as.v;
+            a1 += as.d1;
+        }
+    }
+    EvalF1 e;
+    e.a = a;
+    e.p = rho - a + rho * a1;
+    e.mu = a1;
+    return e;
 }
 
 PCS_DEV bool finitef(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
@@ -317,6 +397,10 @@ struct PreState {
     EvalF l;              // liquid state at rl (re-evaluated or carried by the Taylor expansion)
     float dpv;            // dp/drho of the vapour at its last evaluation
     float sl_prev, sv_prev;
+    float pv, dv_taken;   // vapour pressure at its last evaluation and the step taken from there (carry_slope)
+    float ev;             // estimated relative error of the carried slope dpv (0 after a full evaluation)
+    float sec_prev, d_prev;  // the last pressure quotient and its step (d_prev = 0: none since the last full evaluation)
+    bool lean_v;          // the lane's next vapour evaluation may be the one without the second derivative
     int it, n_liq, code;  // coupled iterations done; diagnostics
     bool ok, done;
 };
@@ -324,6 +408,7 @@ struct PreState {
 PCS_DEV void presolve_begin(const PureCoefF& f, PreState& s) {
     s.n_liq = 0; s.it = 0; s.code = 0;
     s.dpv = 1.0f; s.sl_prev = 1.0f; s.sv_prev = 1.0f;
+    s.pv = 0.0f; s.dv_taken = 0.0f; s.ev = 0.0f; s.sec_prev = 0.0f; s.d_prev = 0.0f; s.lean_v = false;
     // zero-pressure liquid, handed over to the coupled iteration at a loose step
     bool ok = liquid_root_f32(f, 0.0f, PCS_F32_LIQ_TOL, 1e-2f, 12, s.rl, s.n_liq);
     const float rl = s.rl;
@@ -352,39 +437,96 @@ PCS_DEV void presolve_begin(const PureCoefF& f, PreState& s) {
     s.done = !ok;
 }
 
+// Update of the carried vapour slope dp (at the last evaluation, pressure p0) from the pressure p1 one step `drho` further.
+// First update after a full evaluation (d_prev == 0): the trapezoid rule 2 (p1 - p0)/drho - dp, dp/drho at the new point up
+// to p''' drho^2 / 12.  Later updates: the derivative at the new point of the parabola through the last three evaluations,
+// from the two quotients sec_prev (over d_prev) and sec (over drho): sec + (sec - sec_prev) drho / (d_prev + drho), error
+// ~ p''' d_prev drho / 6 -- it forgets the error of the older slope as the steps shrink; taken only when the step has at
+// least halved (two steps of opposite sign and like size would divide by their small sum).  `s` = |drho|/rho of the step,
+// `mu` = a' at the new point (noise model: PCS_F32_SECANT_MIN); a step below the noise threshold keeps the slope.
+// Returns false when the result is unusable (not finite or not positive: the lane then takes the full evaluation at the
+// same density).  `err`: estimated relative error of the slope, a quarter of the squared relative change after a
+// trapezoid update (three times the rule's own term), the geometric mean of that and the previous estimate afterwards.
+PCS_DEV bool carry_slope(float p0, float p1, float drho, float s, float mu, float& dp, float& err, float& sec_prev, float& d_prev) {
+    if (!(s * dp >= PCS_F32_SECANT_MIN * (1.0f + fabsf(mu)))) {
+        d_prev = 0.0f;
+        return true;
+    }
+    const float sec = (p1 - p0) * __builtin_amdgcn_rcpf(drho);
+    const bool three = d_prev != 0.0f && fabsf(drho) <= 0.5f * fabsf(d_prev);
+    const float cand = three ? fmaf(sec - sec_prev, drho * __builtin_amdgcn_rcpf(d_prev + drho), sec) : fmaf(2.0f, sec, -dp);
+    if (!finitef(cand) || !(cand > 0.0f)) return false;
+    const float rel = fabsf(cand * __builtin_amdgcn_rcpf(dp) - 1.0f);
+    err = three ? 0.5f * rel * __builtin_amdgcn_sqrtf(err) : 0.25f * rel * rel;
+    dp = cand;
+    sec_prev = sec;
+    d_prev = drho;
+    return true;
+}
+
 PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
     float rl = s.rl, rv = s.rv;
     EvalF l = s.l;
     bool ok = s.ok, done = s.done;
     float dpv_last = s.dpv, dl_taken = 0.0f;
     float sl_prev = s.sl_prev, sv_prev = s.sv_prev;
+    float pv_last = s.pv, dv_taken = s.dv_taken, ev = s.ev, sec_prev = s.sec_prev, d_prev = s.d_prev;
+    bool lean_v = s.lean_v;
     int n_cpl = s.it;
     // lanes of one wave may resume at different iteration numbers (straggler exchange): `it` below only bounds the loop,
     // the lane's own count n_cpl decides what the first-iteration rule of the stop criterion sees
     for (int it = 0; it < it_end; it++) {
         const bool act = !done && n_cpl < it_end;
+        // Vapour evaluation.  A lane's first one computes a, a', a'' (pure_eval_f32).  From its second iteration on
+        // a'' -- used for dp/drho, the slope of the Newton step, only -- is not computed: the lane evaluates a and a'
+        // (pure_eval1_f32) and carries the slope (carry_slope), unless its last step was taken in ln(rho) or was larger
+        // than PCS_F32_LEAN_MAX, or the carried slope turns out unusable.  The choice depends on the lane's own state
+        // only; a form is executed when some lane of the wave takes it.
+        EvalF v;
+        v.a = 0.0f; v.p = 0.0f; v.mu = 0.0f;
+        bool full = act && !lean_v;
+        const bool lean = act && lean_v;
+        if (__ballot(lean) != 0ull) {
+            if (lean) {
+                const EvalF1 e = pure_eval1_f32(f, rv);
+                v.a = e.a; v.p = e.p; v.mu = e.mu;
+                full = !carry_slope(pv_last, e.p, dv_taken, sv_prev, e.mu, dpv_last, ev, sec_prev, d_prev);
+            }
+        }
+        if (__ballot(full) != 0ull) {
+            if (full) {
+                v = pure_eval_f32(f, rv);
+                dpv_last = v.dp;
+                ev = 0.0f;
+                d_prev = 0.0f;
+            }
+        }
         if (act) {
-            EvalF v = pure_eval_f32(f, rv);
-            dpv_last = v.dp;
+            v.dp = dpv_last;
+            pv_last = v.p;
             float iv = __builtin_amdgcn_rcpf(rv), il = __builtin_amdgcn_rcpf(rl);
             float ps = -(v.a * iv - l.a * il + f_log(rv * il)) * __builtin_amdgcn_rcpf(iv - il);
             float dl = -(l.p - ps) * __builtin_amdgcn_rcpf(l.dp);
             float dv = -(v.p - ps) * __builtin_amdgcn_rcpf(v.dp);
             float rln = rl + dl, rvn = rv + dv;
             // a large downward vapour step (poor first estimate at very low pressures) is taken in ln(rho) instead
-            if (rvn < 0.3f * rv) rvn = rv * f_exp(dv * iv);
+            const bool log_step = rvn < 0.3f * rv;
+            if (log_step) rvn = rv * f_exp(dv * iv);
             if (!finitef(rln) || !finitef(rvn) || !(v.dp > 0.0f) || !(l.dp > 0.0f) || !(rvn > 1e-30f) || !(rvn < 0.6f * rln)) {
                 s.code = (!finitef(rln) || !finitef(rvn)) ? 10 : !(v.dp > 0.0f) ? 11 : !(l.dp > 0.0f) ? 12 : !(rvn > 1e-30f) ? 13 : 14;
                 ok = false;
                 done = true;
             } else {
-                // quadratic convergence: |next step| ~ C step^2 with C estimated from the last two steps
+                // |next step| ~ step (C step + e): C step^2 is Newton's quadratic term with C estimated from the last two
+                // steps, e step the linear term that a slope with the relative error e leaves (0 after a full evaluation)
                 float sl = fabsf(dl) * il, sv = fabsf(dv) * iv;
                 float pl = sl * sl * fminf(sl * __builtin_amdgcn_rcpf(sl_prev * sl_prev), PCS_F32_PREDICT_CMAX);
-                float pv = sv * sv * fminf(sv * __builtin_amdgcn_rcpf(sv_prev * sv_prev), PCS_F32_PREDICT_CMAX);
+                float pv = sv * fmaf(sv, fminf(sv * __builtin_amdgcn_rcpf(sv_prev * sv_prev), PCS_F32_PREDICT_CMAX), ev);
                 done = ((sl <= 2e-6f) && (sv <= 3e-5f)) || (n_cpl > 0 && sl < 1e-2f && sv < 1e-2f && pl <= PCS_F32_PREDICT_TOL_L && pv <= PCS_F32_PREDICT_TOL_V);
                 sl_prev = sl; sv_prev = sv;
                 dl_taken = rln - rl;
+                dv_taken = rvn - rv;
+                lean_v = !log_step && sv <= PCS_F32_LEAN_MAX;
                 rl = rln;
                 rv = rvn;
             }
@@ -395,7 +537,8 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
         // liquid state to the new density by the Taylor expansion (a to 2nd, p to 1st order, dp kept) instead of a
         // re-evaluation; the error (~2.5 (dl/rho)^2 in the density) is below the fp32 noise the pass stops at.  The
         // choice is per lane (a row's result does not depend on its wave-mates); the evaluation is skipped when no
-        // lane of the wave needs it.
+        // lane of the wave needs it.  The re-evaluation is always the full one: the liquid slope is
+        // steep and strongly curved (rho p''/p' ~ 10-20), and a wave rarely has no lane whose liquid step needs it.
         {
             const bool moved = act && !done;
             const bool reeval = moved && !(fabsf(dl_taken) <= PCS_F32_TAYLOR_MAX * rl);
@@ -412,6 +555,7 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
         if (__ballot(!done && n_cpl < it_end) == 0ull) break;
     }
     s.rl = rl; s.rv = rv; s.l = l; s.dpv = dpv_last; s.sl_prev = sl_prev; s.sv_prev = sv_prev;
+    s.pv = pv_last; s.dv_taken = dv_taken; s.ev = ev; s.sec_prev = sec_prev; s.d_prev = d_prev; s.lean_v = lean_v;
     s.it = n_cpl; s.ok = ok; s.done = done;
 }
 
