@@ -34,6 +34,7 @@ SIGNATURES = {
     "pcs_pure_vle_retry": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_liquid_density": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcs_pure_derivatives": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pcs_pure_start_probe": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "pcs_pure_jacobian": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pcs_pure_jacobian_vjp": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcs_pure_critical_point": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

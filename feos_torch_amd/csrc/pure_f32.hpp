@@ -101,11 +101,14 @@ PCS_DEV F1 hornerf(const float* coef, F1 x) {
 
 struct PureCoefF {
     float m, mm1, ceta, ai[7], bi[7], kd1, kd2, j1[5], j2[4], qm, da, na, nb;
+    float m1, m2;  // (m-1)/m, (m-2)/m: ai[] / bi[] are linear in m1 and m1 m2 (read by pure_eval_start_f32 only)
     bool polar, assoc;
 };
 
 PCS_DEV void to_f32(const PureCoef<double>& c, PureCoefF& f) {
     f.m = (float)c.m; f.mm1 = (float)c.mm1; f.ceta = (float)c.ceta;
+    const float rm = __builtin_amdgcn_rcpf(f.m);
+    f.m1 = f.mm1 * rm; f.m2 = (f.m - 2.0f) * rm;
 #pragma unroll
     for (int i = 0; i < 7; i++) { f.ai[i] = (float)c.ai[i]; f.bi[i] = (float)c.bi[i]; }
     f.kd1 = (float)c.kd1; f.kd2 = (float)c.kd2;
@@ -135,6 +138,8 @@ PCS_DEV void pure_coef_f32(PureCoefF& f, const double* par, double T64) {
     const float rm = __builtin_amdgcn_rcpf(m);
     const float m1 = f.mm1 * rm;
     const float m2 = (m - 2.0f) * rm;
+    f.m1 = m1;
+    f.m2 = m2;
 #pragma unroll
     for (int i = 0; i < 7; i++) {
         f.ai[i] = fmaf(m1, fmaf(m2, (float)A2[i], (float)A1[i]), (float)A0[i]);
@@ -235,6 +240,24 @@ PCS_DEV F2 core_closed_f32(const PureCoefF& c, float rho) {
     return a;
 }
 
+// Site fractions XA, XB of a pure component at S = rho Delta from the cancellation-free closed forms of pure_model.hpp.
+PCS_DEV void assoc_sites_f32(const PureCoefF& c, float S, float& xa, float& xb) {
+    const float sa = c.na * S, sb = c.nb * S;  // rho_a Delta, rho_b Delta
+    const float t = sb - sa;
+    const float aux = 1.0f - t;
+    const float sq = __builtin_amdgcn_sqrtf(fmaf(aux, aux, 4.0f * sb));
+    if (t > 0.5f) {
+        xa = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f + t);
+        xb = (sq - 1.0f + t) * __builtin_amdgcn_rcpf(2.0f * sb);
+    } else if (t < -0.5f) {
+        xa = (sq - 1.0f - t) * __builtin_amdgcn_rcpf(2.0f * sa);
+        xb = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f - t);
+    } else {
+        xa = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f + t);
+        xb = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f - t);
+    }
+}
+
 // Association term of a pure component in closed form (value, first and second density derivative).
 //   a_assoc = rho q(S),  q = na (ln XA - XA/2 + 1/2) + nb (ln XB - XB/2 + 1/2),  S = rho Delta(eta) = rho da h(eta),
 //   h = u + 1.5 eta u^2 + 0.5 eta^2 u^3,  u = 1/(1-eta)                                  (pcsaft_pure.py:163-176)
@@ -256,21 +279,8 @@ PCS_DEV F2 assoc_closed_f32(const PureCoefF& c, float rho) {
     const float h1 = u2 * (2.5f + eu * (4.0f + 1.5f * eu));
     const float S = rho * c.da * h;
     const float S1 = c.da * (h + eta * h1);
-    const float sa = c.na * S, sb = c.nb * S;  // rho_a Delta, rho_b Delta
-    const float t = sb - sa;
-    const float aux = 1.0f - t;
-    const float sq = __builtin_amdgcn_sqrtf(fmaf(aux, aux, 4.0f * sb));
     float xa, xb;
-    if (t > 0.5f) {
-        xa = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f + t);
-        xb = (sq - 1.0f + t) * __builtin_amdgcn_rcpf(2.0f * sb);
-    } else if (t < -0.5f) {
-        xa = (sq - 1.0f - t) * __builtin_amdgcn_rcpf(2.0f * sa);
-        xb = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f - t);
-    } else {
-        xa = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f + t);
-        xb = 2.0f * __builtin_amdgcn_rcpf(sq + 1.0f - t);
-    }
+    assoc_sites_f32(c, S, xa, xb);
     const float q = c.na * (f_log(xa) - 0.5f * xa + 0.5f) + c.nb * (f_log(xb) - 0.5f * xb + 0.5f);
     const float nn = c.na * c.nb;
     const float q1 = -nn * xa * xb;
@@ -342,45 +352,224 @@ PCS_DEV EvalF1 pure_eval1_f32(const PureCoefF& c, float rho) {
     return e;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// The evaluation at the start density of the liquid root.  Every lane starts at rho0 = PCS_F32_START_ETA / ceta, i.e. at
+// the same packing fraction eta0, where everything in the closed forms above that depends on eta alone is a number: u, w and
+// their powers, HS, ln g, A, B with their derivatives (two reciprocals and the logarithm), and the polynomials I1, I2, whose
+// coefficients are ai[i] = A0[i] + m1 (A1[i] + m2 A2[i]), reduce to three eta-moments of the universal tables each.  The
+// derivatives are taken in t = rho / rho0 at t = 1 (x_t = rho x', x_tt = rho^2 x''): eta_t = eta0, so the chain-rule factors
+// are numbers as well, and p = rho0 - a + a_t, a' = a_t / rho0, dp/drho = 1 + a_tt / rho0.  All constants are derived here at
+// compile time, in double, from PCS_F32_START_ETA and pcsaft_consts.hpp.
+constexpr float PCS_F32_START_ETA = 0.5f;
+
+struct StartMom { double v, t, tt; };  // x, eta x', eta^2 x'' at eta0
+struct StartPow { float v[7], t[7], tt[7]; };  // eta0^i, i eta0^i, i (i-1) eta0^i
+struct StartConst {
+    double u;                   // 1 / (1 - eta0)
+    StartMom HS, LG, A, B, H;   // H: S = rho Delta = rho0 da t h(eta0 t) -> S, S_t, S_tt in units of rho0 da
+    StartMom SA[3], SB[3];      // moments of A0, A1, A2 / B0, B1, B2
+    StartPow pw;
+};
+constexpr double start_atanh2(double z) {  // 2 atanh(z), |z| <= 1/3
+    double sum = 0.0, zp = z;
+    for (int k = 1; k < 80; k += 2) { sum += zp / k; zp *= z * z; }
+    return 2.0 * sum;
+}
+constexpr double start_log(double x) {  // ln x, x > 0
+    int k = 0;
+    while (x > 1.5) { x *= 0.5; k++; }
+    while (x < 0.75) { x *= 2.0; k--; }
+    return k * start_atanh2(1.0 / 3.0) + start_atanh2((x - 1.0) / (x + 1.0));
+}
+template <int N>
+constexpr StartMom start_moments(const double (&c)[N], double e) {
+    StartMom r = {0.0, 0.0, 0.0};
+    double pw = 1.0;
+    for (int i = 0; i < N; i++) { r.v += c[i] * pw; r.t += i * c[i] * pw; r.tt += i * (i - 1) * c[i] * pw; pw *= e; }
+    return r;
+}
+template <int N>
+constexpr StartMom start_horner(const double (&c)[N], double e) {  // the recurrences of horner3f
+    double p = c[N - 1], d1 = 0.0, h = 0.0;
+    for (int i = N - 2; i >= 0; i--) { h = h * e + d1; d1 = d1 * e + p; p = p * e + c[i]; }
+    return StartMom{p, e * d1, e * e * 2.0 * h};
+}
+constexpr bool start_close(double a, double b) { return (a - b) * (a - b) <= 1e-24 * (1.0 + a * a); }
+constexpr bool start_close(const StartMom& a, const StartMom& b) { return start_close(a.v, b.v) && start_close(a.t, b.t) && start_close(a.tt, b.tt); }
+constexpr StartConst start_const(double e) {
+    StartConst k = {};
+    const double u = 1.0 / (1.0 - e), w = 1.0 / (2.0 - e);
+    const double u2 = u * u, u3 = u2 * u, u4 = u2 * u2, w2 = w * w;
+    k.u = u;
+    k.HS = StartMom{e * (4.0 - 3.0 * e) * u2, e * (4.0 - 2.0 * e) * u3, e * e * (10.0 - 4.0 * e) * u4};
+    k.LG = StartMom{start_log((1.0 - 0.5 * e) * u3), e * (3.0 * u - w), e * e * (3.0 * u2 - w2)};
+    k.A = StartMom{e * (8.0 - 2.0 * e) * u4, e * (8.0 + e * (20.0 - 4.0 * e)) * (u4 * u), e * e * (60.0 + e * (72.0 - 12.0 * e)) * (u4 * u2)};
+    const double poly = e * (20.0 + e * (-27.0 + e * (12.0 - 2.0 * e)));
+    const double poly1 = 20.0 + e * (-54.0 + e * (36.0 - 8.0 * e)), poly2 = -54.0 + e * (72.0 - 24.0 * e);
+    const double q = u2 * w2, s = u + w, t = poly1 + 2.0 * poly * s;
+    k.B = StartMom{poly * q, e * (q * t), e * e * (q * (2.0 * s * t + poly2 + 2.0 * poly1 * s + 2.0 * poly * (u2 + w2)))};
+    const double eu = e * u;
+    const double h = u * (1.0 + eu * (1.5 + 0.5 * eu)), h1 = u2 * (2.5 + eu * (4.0 + 1.5 * eu)), h2 = u3 * (9.0 + eu * (15.0 + 6.0 * eu));
+    k.H = StartMom{h, h + e * h1, 2.0 * e * h1 + e * e * h2};
+    k.SA[0] = start_moments(A0, e); k.SA[1] = start_moments(A1, e); k.SA[2] = start_moments(A2, e);
+    k.SB[0] = start_moments(B0, e); k.SB[1] = start_moments(B1, e); k.SB[2] = start_moments(B2, e);
+    double pw = 1.0;
+    for (int i = 0; i < 7; i++) { k.pw.v[i] = (float)pw; k.pw.t[i] = (float)(i * pw); k.pw.tt[i] = (float)(i * (i - 1) * pw); pw *= e; }
+    return k;
+}
+constexpr StartConst START = start_const((double)PCS_F32_START_ETA);
+static_assert(PCS_F32_START_ETA > 0.0f && PCS_F32_START_ETA < 1.0f, "start packing fraction");
+static_assert(start_close(START.SA[0], start_horner(A0, (double)PCS_F32_START_ETA)) && start_close(START.SA[1], start_horner(A1, (double)PCS_F32_START_ETA)) &&
+              start_close(START.SA[2], start_horner(A2, (double)PCS_F32_START_ETA)), "eta-moments of A0..A2 against their Horner evaluation");
+static_assert(start_close(START.SB[0], start_horner(B0, (double)PCS_F32_START_ETA)) && start_close(START.SB[1], start_horner(B1, (double)PCS_F32_START_ETA)) &&
+              start_close(START.SB[2], start_horner(B2, (double)PCS_F32_START_ETA)), "eta-moments of B0..B2 against their Horner evaluation");
+static_assert(start_close(start_log(6.0), 2.0 * start_log(2.0) + start_log(1.5)) && start_close(start_log(0.001) + start_log(1000.0), 0.0) &&
+              start_close(start_log(2.718281828459045), 1.0), "compile-time logarithm");
+
+PCS_DEV float start_rho_f32(const PureCoefF& c) { return PCS_F32_START_ETA / c.ceta; }
+
+// (a, p, dp, mu) of pure_eval_f32(c, start_rho_f32(c)); what remains per row is linear in m, m-1, m1, m1 m2, the reciprocal of
+// D, the dot products of the row's dipole coefficients with the powers of eta0, and the site fractions.
+PCS_DEV EvalF pure_eval_start_f32(const PureCoefF& c) {
+    constexpr StartConst K = START;
+    const float rho = start_rho_f32(c);
+    const float F = c.m * (float)K.HS.v - c.mm1 * (float)K.LG.v;
+    const float Ft = c.m * (float)K.HS.t - c.mm1 * (float)K.LG.t;
+    const float Ftt = c.m * (float)K.HS.tt - c.mm1 * (float)K.LG.tt;
+    const float m1 = c.m1, m2 = c.m2;
+    const float I1 = fmaf(m1, fmaf(m2, (float)K.SA[2].v, (float)K.SA[1].v), (float)K.SA[0].v);
+    const float I1t = fmaf(m1, fmaf(m2, (float)K.SA[2].t, (float)K.SA[1].t), (float)K.SA[0].t);
+    const float I1tt = fmaf(m1, fmaf(m2, (float)K.SA[2].tt, (float)K.SA[1].tt), (float)K.SA[0].tt);
+    const float I2 = fmaf(m1, fmaf(m2, (float)K.SB[2].v, (float)K.SB[1].v), (float)K.SB[0].v);
+    const float I2t = fmaf(m1, fmaf(m2, (float)K.SB[2].t, (float)K.SB[1].t), (float)K.SB[0].t);
+    const float I2tt = fmaf(m1, fmaf(m2, (float)K.SB[2].tt, (float)K.SB[1].tt), (float)K.SB[0].tt);
+    const float D = 1.0f + c.m * (float)K.A.v - c.mm1 * (float)K.B.v;
+    const float Dt = c.m * (float)K.A.t - c.mm1 * (float)K.B.t;
+    const float Dtt = c.m * (float)K.A.tt - c.mm1 * (float)K.B.tt;
+    const float C = __builtin_amdgcn_rcpf(D), Csq = C * C;
+    const float Ct = -Dt * Csq;
+    const float Ctt = (2.0f * Dt * Dt * C - Dtt) * Csq;
+    const float G = c.kd1 * I1 + c.kd2 * (C * I2);
+    const float Gt = c.kd1 * I1t + c.kd2 * (Ct * I2 + C * I2t);
+    const float Gtt = c.kd1 * I1tt + c.kd2 * (Ctt * I2 + 2.0f * Ct * I2t + C * I2tt);
+    float a = rho * (F + rho * G);
+    float at = rho * (F + Ft + rho * (2.0f * G + Gt));
+    float att = rho * (2.0f * Ft + Ftt + rho * (2.0f * G + 4.0f * Gt + Gtt));
+    if (c.polar || c.assoc) {
+        if (c.polar) {
+            // a = rho^2 qm J1^2 / (J1 - rho J2) = (rho0^2 qm) t^2 Q(t),  Q = J1^2 / (J1 - t N),  N = rho0 J2
+            float j1v = c.j1[0], j1t = 0.0f, j1tt = 0.0f, j2v = c.j2[0], j2t = 0.0f, j2tt = 0.0f;
+#pragma unroll
+            for (int i = 1; i < 5; i++) {
+                j1v = fmaf(c.j1[i], K.pw.v[i], j1v);
+                j1t = fmaf(c.j1[i], K.pw.t[i], j1t);
+                if (i > 1) j1tt = fmaf(c.j1[i], K.pw.tt[i], j1tt);
+            }
+#pragma unroll
+            for (int i = 1; i < 4; i++) {
+                j2v = fmaf(c.j2[i], K.pw.v[i], j2v);
+                j2t = fmaf(c.j2[i], K.pw.t[i], j2t);
+                if (i > 1) j2tt = fmaf(c.j2[i], K.pw.tt[i], j2tt);
+            }
+            const F2 J1 = f2(j1v, j1t, j1tt);
+            const F2 N = f2(j2v, j2t, j2tt) * rho;
+            const F2 Q = (J1 * J1) * recipf(J1 - f2(N.v, N.d1 + N.v, N.d2 + 2.0f * N.d1));
+            const float k = (rho * rho) * c.qm;
+            a = fmaf(k, Q.v, a);
+            at = fmaf(k, Q.d1 + 2.0f * Q.v, at);
+            att = fmaf(k, Q.d2 + 4.0f * Q.d1 + 2.0f * Q.v, att);
+        }
+        if (c.assoc) {
+            // assoc_closed_f32 with S, S_t, S_tt = (rho0 da) (h, h + eta0 h', 2 eta0 h' + eta0^2 h'')
+            const float rd = rho * c.da;
+            const float S = rd * (float)K.H.v, St = rd * (float)K.H.t, Stt = rd * (float)K.H.tt;
+            float xa, xb;
+            assoc_sites_f32(c, S, xa, xb);
+            const float q = c.na * (f_log(xa) - 0.5f * xa + 0.5f) + c.nb * (f_log(xb) - 0.5f * xb + 0.5f);
+            const float nn = c.na * c.nb;
+            const float q1 = -nn * xa * xb;
+            const float al = c.nb * xa * xa, be = c.na * xb * xb;
+            const float rden = __builtin_amdgcn_rcpf(1.0f - al * be * S * S);
+            const float xa1 = al * (be * S * xa - xb) * rden, xb1 = be * (al * S * xb - xa) * rden;
+            const float q2 = -nn * (xa1 * xb + xa * xb1);
+            a = fmaf(rho, q, a);
+            at = fmaf(rho, q + q1 * St, at);
+            att = fmaf(rho, q1 * (2.0f * St + Stt) + q2 * St * St, att);
+        }
+    }
+    const float ir = c.ceta * (1.0f / PCS_F32_START_ETA);  // 1 / rho0
+    EvalF e;
+    e.a = a;
+    e.p = rho - a + at;
+    e.dp = fmaf(att, ir, 1.0f);
+    e.mu = at * ir;
+    return e;
+}
+
 PCS_DEV bool finitef(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+struct LiquidRootF {
+    float rl;
+    bool ok, done, dense;
+    int first;  // iteration at which the current start density is evaluated
+};
+// One iteration of liquid_root_f32 from the evaluation `e` at s.rl.  AT_START: s.rl is the start density (iteration 0).
+template <bool AT_START>
+PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float tol_dense, int it, const EvalF& e, LiquidRootF& s) {
+    const float res = e.p - p_spec;
+    if (it == s.first && it < PCS_F32_DENSE_LEVELS && finitef(e.p) && !(res > 0.0f)) {
+        // still on the dilute side of the root: next start 0.08 further up (eta = 0.58, 0.66, 0.74)
+        s.dense = true;
+        s.first = it + 1;
+        s.rl = (0.58f + 0.08f * (float)it) / f.ceta;
+    } else if (!finitef(e.p) || !(e.dp > 0.0f) || (it == s.first && !(res > 0.0f))) {
+        s.ok = false;
+        s.done = true;
+    } else {
+        const float u = AT_START ? (float)START.u : __builtin_amdgcn_rcpf(1.0f - s.rl * f.ceta);
+        float den = s.dense ? e.dp : e.dp - 4.0f * res * f.ceta * u;
+        float step = res * __builtin_amdgcn_rcpf(den);
+        if (!(den > 0.0f)) step = 2.0f * s.rl;  // -> rn < 0 -> this lane takes the fp64 initialiser
+        float rn = s.rl - step;
+        if (!(rn > 0.0f)) { s.ok = false; s.done = true; }
+        else { s.done = fabsf(step) <= (s.dense ? tol_dense : tol) * s.rl; s.rl = rn; }
+    }
+}
 // fp32 liquid root of p(rho) = p_spec from eta = 0.5.  Newton on (p - p_spec)(1-eta)^4 = 0 (same root):
 // the hard-sphere pole makes p(rho) very steep on the dense side, the scaled function is close to
 // linear -> 2-3 evaluations instead of 4-6 to a 10 % step.  Strongly attractive rows (large dipole /
 // association at low T) have their liquid above eta = 0.5: they restart at eta = 0.58 on its dense side
 // with plain Newton (monotone from there) and the tighter `tol_dense`.
-// Wave-uniform loop; returns false when the lane must use the fp64 initialiser.
+// Wave-uniform loop; returns false when the lane must use the fp64 initialiser.  Iteration 0 is peeled: every lane is at
+// eta0 there and takes pure_eval_start_f32.
 PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float tol_dense, int cap, float& rl,
                              int& n_eval) {
-    bool ok = finitef(f.da) && finitef(f.kd2) && finitef(f.ceta) && f.ceta > 0.0f && finitef(p_spec);
-    rl = 0.5f / f.ceta;
-    bool done = !ok, dense = false;
-    int first = 0;  // iteration at which the current start density is evaluated
-    for (int it = 0; it < cap; it++) {
-        if (!done) {
-            EvalF e = pure_eval_f32(f, rl);
+    LiquidRootF s;
+    s.ok = finitef(f.da) && finitef(f.kd2) && finitef(f.ceta) && f.ceta > 0.0f && finitef(p_spec);
+    s.rl = start_rho_f32(f);
+    s.done = !s.ok;
+    s.dense = false;
+    s.first = 0;
+    // iteration 0: every lane is at eta0 -> the fixed-eta evaluation (wave-uniform, no second body per lane).  The
+    // dense-side restarts share their iterations with other lanes' Newton evaluations and stay generic.
+    if (cap > 0) {
+        if (!s.done) {
+            liquid_root_step<true>(f, p_spec, tol, tol_dense, 0, pure_eval_start_f32(f), s);
             n_eval++;
-            float res = e.p - p_spec;
-            if (it == first && it < PCS_F32_DENSE_LEVELS && finitef(e.p) && !(res > 0.0f)) {
-                // still on the dilute side of the root: next start 0.08 further up (eta = 0.58, 0.66, 0.74)
-                dense = true;
-                first = it + 1;
-                rl = (0.58f + 0.08f * (float)it) / f.ceta;
-            } else if (!finitef(e.p) || !(e.dp > 0.0f) || (it == first && !(res > 0.0f))) {
-                ok = false;
-                done = true;
-            } else {
-                float den = dense ? e.dp : e.dp - 4.0f * res * f.ceta * __builtin_amdgcn_rcpf(1.0f - rl * f.ceta);
-                float step = res * __builtin_amdgcn_rcpf(den);
-                if (!(den > 0.0f)) step = 2.0f * rl;  // -> rn < 0 -> this lane takes the fp64 initialiser
-                float rn = rl - step;
-                if (!(rn > 0.0f)) { ok = false; done = true; }
-                else { done = fabsf(step) <= (dense ? tol_dense : tol) * rl; rl = rn; }
+        }
+        if (__ballot(!s.done) != 0ull) {
+#pragma unroll 1
+            for (int it = 1; it < cap; it++) {
+                if (!s.done) {
+                    liquid_root_step<false>(f, p_spec, tol, tol_dense, it, pure_eval_f32(f, s.rl), s);
+                    n_eval++;
+                }
+                if (__ballot(!s.done) == 0ull) break;
             }
         }
-        if (__ballot(!done) == 0ull) break;
     }
-    return ok && done;
+    rl = s.rl;
+    return s.ok && s.done;
 }
 
 // fp32 pass, in two resumable parts so that a kernel can hand the few lanes that need more coupled iterations than their

@@ -341,6 +341,26 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------
+// test probe: the evaluation the fp32 liquid root starts from, in its generic and its fixed-eta form
+// ------------------------------------------------------------------------------------------
+// out[i] = (a, p, dp, mu) of pure_eval_f32(f, start_rho_f32(f)), then the same four of pure_eval_start_f32(f)
+__global__ __launch_bounds__(BLOCK) void k_pure_start_probe(const double* __restrict__ params, const double* __restrict__ temp,
+                                                            int64_t n, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double par[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) par[k] = params[8 * i + k];
+    PureCoefF f;
+    pure_coef_f32(f, par, temp[i]);
+    const EvalF g = pure_eval_f32(f, start_rho_f32(f));
+    const EvalF s = pure_eval_start_f32(f);
+    float* o = out + 8 * i;
+    o[0] = g.a; o[1] = g.p; o[2] = g.dp; o[3] = g.mu;
+    o[4] = s.a; o[5] = s.p; o[6] = s.dp; o[7] = s.mu;
+}
+
+// ------------------------------------------------------------------------------------------
 // K4: Jacobian of a property w.r.t. (8 parameters, T, p) at fixed densities
 // ------------------------------------------------------------------------------------------
 template <int WHICH>
@@ -467,8 +487,9 @@ int launch_pure_liquid_density(const double* params, const double* temp, const d
 #if PCS_PURE_PART == 1
 extern "C" {
 
-int pcs_abi_version(void) { return 106; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
-                                            // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp)
+int pcs_abi_version(void) { return 107; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+                                            // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp);
+                                            // 107: pcs_pure_start_probe
 
 const char* pcs_last_error(void) { return g_err; }
 
@@ -587,6 +608,18 @@ int pcs_pure_derivatives(const double* params, const double* temp, const double*
                        dp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("k_pure_derivatives launch", e);
+    return 0;
+}
+
+int pcs_pure_start_probe(const double* params, const double* temp, int64_t n, float* out, void* stream) {
+    g_err[0] = 0;
+    if (int e = check_n(n)) return e;
+    if (n == 0) return 0;
+    if (!params || !temp || !out) return fail_msg("pcs_pure_start_probe: null required pointer");
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_pure_start_probe, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, temp, n, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("k_pure_start_probe launch", e);
     return 0;
 }
 

@@ -109,6 +109,14 @@ int pcs_pure_derivatives(const double* params, const double* temp, const double*
                          double* p, double* dp, void* stream);
 
 /*
+ * Test probe of the fp32 pre-solve: the model evaluation its liquid root starts from (rho = 0.5 / ceta, packing fraction
+ * 0.5), in fp32 as the kernels compute it.
+ *   out [n,8] float  (a, p, dp/drho, a') from the generic evaluation, then the same four from the closed form at the
+ *                    fixed packing fraction that the first iteration of the root uses.  All reduced (A^-3).
+ */
+int pcs_pure_start_probe(const double* params, const double* temp, int64_t n, float* out, void* stream);
+
+/*
  * Jacobian of a pure-component property w.r.t. its inputs with the phase densities held
  * fixed — what torch reverse mode through the reference's Python tail yields
  * (feos_torch/pcsaft_pure.py:196-199 / :212-215 / :228-233).
