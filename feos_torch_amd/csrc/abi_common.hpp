@@ -16,12 +16,36 @@ inline int fail_msg(const char* what) {
     snprintf(g_err, sizeof(g_err), "%s", what);
     return 2;
 }
+inline int fail_msg(const char* entry, const char* what) {  // "<entry>: <what>"
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, what);
+    return 2;
+}
 inline int check_n(int64_t n) {
     if (n < 0) return fail_msg("n must be >= 0");
     if (n >= (int64_t)1 << 31) return fail_msg("n must be < 2^31 rows per call (shard larger batches)");
     return 0;
 }
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Start of every entry point: clears the error string and checks n and the required pointers (the caller spells them out:
+// `params && temp && ...`).  GO_ON: launch; anything else is the entry point's return value (0 for an empty batch).
+constexpr int GO_ON = -1;
+inline int enter(int64_t n, bool required_present, const char* null_message) {
+    g_err[0] = 0;
+    if (int e = check_n(n)) return e;
+    if (n == 0) return 0;
+    if (!required_present) return fail_msg(null_message);
+    return GO_ON;
+}
+
+// End of every launch sequence: 0, or the pending launch error under the name `what`
+inline int launched(const char* what) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(what, e);
+}
+
+// workgroups of `block` lanes that cover n rows
+inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 // Device-side counters (retry-list count, work-queue control block) are zeroed by a KERNEL on the call's stream, not by
 // hipMemsetAsync: every operation of a call is then a kernel node of a hipGraph capture.  What round 2's one A/B run shows
@@ -39,9 +63,7 @@ __global__ void k_zero_ints(int32_t* __restrict__ p, int count) {
 }
 inline int zero_ints(int32_t* p, int count, hipStream_t s) {
     hipLaunchKernelGGL(k_zero_ints<0>, dim3(1), dim3(64), 0, s, p, count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_zero_ints launch", e);
-    return 0;
+    return launched("k_zero_ints launch");
 }
 
 }  // namespace pcs_abi

@@ -169,9 +169,7 @@ int pcs_compact_plan(const uint8_t* status, int64_t n, void* cws, void* stream) 
     const int nb = n > 0 ? compact_blocks(n) : 0;
     if (nb) hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(CTHREADS), 0, s, status, n, w);
     hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, s, w, nb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_compact_scan launch", e);
-    return 0;
+    return launched("k_compact_scan launch");
 }
 
 int pcs_compact_rows(const uint8_t* status, int64_t n, const void* cws, const double* src, int width, double* dst,
@@ -186,9 +184,7 @@ int pcs_compact_rows(const uint8_t* status, int64_t n, const void* cws, const do
     hipLaunchKernelGGL(k_compact_rows, dim3(compact_blocks(n)), dim3(CTHREADS), 0, as_stream(stream), status, n,
                        static_cast<const int32_t*>(cws), src, width, dst, index,
                        (int)(src && (width & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_compact_rows launch", e);
-    return 0;
+    return launched("k_compact_rows launch");
 }
 
 int pcs_expand_rows(const uint8_t* status, int64_t n, const void* cws, const double* g, const double* src, int src_stride,
@@ -200,9 +196,7 @@ int pcs_expand_rows(const uint8_t* status, int64_t n, const void* cws, const dou
     if (ncol < 1 || col0 < 0 || col0 + ncol > src_stride || src_stride > 64) return fail_msg("pcs_expand_rows: bad column range");
     hipLaunchKernelGGL(k_expand_rows, dim3(compact_blocks(n)), dim3(CTHREADS), 0, as_stream(stream), status, n,
                        static_cast<const int32_t*>(cws), g, src, src_stride, col0, ncol, dst);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_expand_rows launch", e);
-    return 0;
+    return launched("k_expand_rows launch");
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
+#include "block_order.hpp"
 #include "gc_model.hpp"
 #include "gc_kernel_common.hpp"
 #include "mix_solver.hpp"
@@ -110,24 +111,12 @@ __global__ __launch_bounds__(GBLOCK) void k_gc_bubble_dew(const double* __restri
         __shared__ int bins[GC_BINS + 1];
         __shared__ int perm[GBLOCK];
         const int t = threadIdx.x;
-        if (t <= GC_BINS) bins[t] = 0;
-        __syncthreads();
-        int key = GC_BINS;  // rows past n sort last
-        if (first < n) key = gc_bucket(rows + (size_t)first * GC_ROW_BYTES, tb);
-        atomicAdd(&bins[key], 1);
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-#pragma unroll
-            for (int b = 0; b <= GC_BINS; b++) {
-                int c = bins[b];
-                bins[b] = acc;
-                acc += c;
-            }
-        }
-        __syncthreads();
-        perm[atomicAdd(&bins[key], 1)] = t;
-        __syncthreads();
+        // rows past n sort last, in a bucket of their own
+        block_order<GC_BINS + 1>(bins, perm, [=] {
+            int key = GC_BINS;
+            if (first < n) key = gc_bucket(rows + (size_t)first * GC_ROW_BYTES, tb);
+            return key;
+        });
         first = (int64_t)blockIdx.x * GBLOCK + perm[t];
     }
     const int64_t total = RETRY ? min((int64_t)max(retry[0], 0), n) : n;  // count and entries bounded by n: a foreign list must not fault
@@ -339,7 +328,7 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
     if (n == 0) return 0;
     if (!table || !rows || !phi || !temp || !z || !p_init || !status) return fail_msg("pcs_gc_bubble_dew: null required pointer");
     if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_bubble_dew: rows must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + GBLOCK - 1) / GBLOCK);
+    const unsigned grid = grid_for(n, GBLOCK);
     const size_t lds = gc_lds_bytes(S, GBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES);
     hipStream_t s = as_stream(stream);
     int32_t* retry = static_cast<int32_t*>(workspace);
@@ -359,9 +348,7 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
             hipLaunchKernelGGL((k_gc_bubble_dew<false, true>), dim3(GC_RETRY_BLOCKS), dim3(GBLOCK), lds, s, table, S, rows, phi,
                                temp, z, p_init, n, p_out, rho4, status, iters, retry, order);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_gc_bubble_dew launch", e);
-    return 0;
+    return launched("k_gc_bubble_dew launch");
 }
 
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
@@ -371,12 +358,10 @@ int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const do
     if (n == 0) return 0;
     if (!table || !rows || !phi || !temp || !rho) return fail_msg("pcs_gc_derivatives: null required pointer");
     if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_derivatives: rows must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + GBLOCK - 1) / GBLOCK);
+    const unsigned grid = grid_for(n, GBLOCK);
     hipLaunchKernelGGL(k_gc_derivatives, dim3(grid), dim3(GBLOCK), gc_lds_bytes(S, GBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES), as_stream(stream),
                        table, S, rows, phi, temp, rho, n, a, p, mu, v);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_gc_derivatives launch", e);
-    return 0;
+    return launched("k_gc_derivatives launch");
 }
 
 int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
@@ -386,7 +371,7 @@ int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, co
     if (n == 0) return 0;
     if (!table || !rows || !phi || !temp || !rho4 || !jac) return fail_msg("pcs_gc_jacobian: null required pointer");
     if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_jacobian: rows must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + GJBLOCK - 1) / GJBLOCK);
+    const unsigned grid = grid_for(n, GJBLOCK);
     // double model: 2*MAXE doubles per thread; dual model dab: 2*MAXE * (1 + GC_CHUNK) doubles per thread
     const size_t lds = gc_lds_bytes(S, GJBLOCK, 2 * GC_MAXE + 2 * GC_MAXE * (1 + GC_CHUNK) + GC_ROW_LDS_DOUBLES);
     if (lds > 64 * 1024) {  // above the default dynamic-LDS limit
@@ -395,9 +380,7 @@ int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, co
     }
     hipLaunchKernelGGL(k_gc_jacobian, dim3(grid), dim3(GJBLOCK), lds, as_stream(stream), dew, table, S, rows, phi, temp,
                        rho4, n, jac, agg, order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_gc_jacobian launch", e);
-    return 0;
+    return launched("k_gc_jacobian launch");
 }
 
 }  // extern "C"

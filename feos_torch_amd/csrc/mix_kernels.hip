@@ -9,6 +9,7 @@
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
+#include "block_order.hpp"
 #include "mix_model.hpp"
 #include <cstddef>
 #include "mix_solver.hpp"
@@ -62,24 +63,8 @@ __global__ __launch_bounds__(MBLOCK, 1) void k_mix_bubble_dew(const double* __re
     __shared__ int bins[MIX_BINS + 1];
     const int t = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * MBLOCK;
-    if (t <= MIX_BINS) bins[t] = 0;
-    __syncthreads();
-    int key = MIX_BINS;  // rows past n sort last
-    if (row0 + t < n) key = mix_bucket(params + 16 * (row0 + t));
-    atomicAdd(&bins[key], 1);
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-#pragma unroll
-        for (int b = 0; b <= MIX_BINS; b++) {
-            int c = bins[b];
-            bins[b] = acc;
-            acc += c;
-        }
-    }
-    __syncthreads();
-    perm[atomicAdd(&bins[key], 1)] = t;
-    __syncthreads();
+    // rows past n sort last, in a bucket of their own
+    block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
     const int64_t i = row0 + perm[t];
     if (i >= n) return;
     double par[16], k0, k1;
@@ -548,24 +533,8 @@ __global__ __launch_bounds__(MBLOCK) void k_mix_jacobian(int dew, const double* 
         i = order[row0 + t];
         if (i < 0 || i >= n) return;
     } else {
-        if (t <= MIX_BINS) bins[t] = 0;
-        __syncthreads();
-        int key = MIX_BINS;
-        if (row0 + t < n) key = mix_bucket(params + 16 * (row0 + t));
-        atomicAdd(&bins[key], 1);
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-#pragma unroll
-            for (int b = 0; b <= MIX_BINS; b++) {
-                int c = bins[b];
-                bins[b] = acc;
-                acc += c;
-            }
-        }
-        __syncthreads();
-        perm[atomicAdd(&bins[key], 1)] = t;
-        __syncthreads();
+        // rows past n sort last, in a bucket of their own
+        block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
         i = row0 + perm[t];
         if (i >= n) return;
     }
@@ -613,6 +582,19 @@ int queue_waves() {
     return waves;
 }
 
+// Batch-wide class order: zeroes the control block behind perm[n] in the workspace and fills perm (expensive classes first).
+// The launches are checked by the caller's launched() at the end of its own sequence.
+int launch_mix_class_order(const double* params, int64_t n, void* workspace, hipStream_t s) {
+    int32_t* perm = static_cast<int32_t*>(workspace);
+    int32_t* ctrl = perm + n;
+    if (int ez = zero_ints(ctrl, QCTRL_INTS, s)) return ez;
+    const unsigned g256 = grid_for(n, 256);
+    hipLaunchKernelGGL(k_mix_class_count, dim3(g256), dim3(256), 0, s, params, n, ctrl);
+    hipLaunchKernelGGL(k_mix_class_scan, dim3(1), dim3(64), 0, s, ctrl);
+    hipLaunchKernelGGL(k_mix_class_scatter, dim3(g256), dim3(256), 0, s, params, n, ctrl, perm);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,10 +610,7 @@ int64_t pcs_mix_workspace_bytes(int64_t n) {
 int pcs_mix_bubble_dew(int dew, const double* params, const double* kij, const double* temp, const double* z,
                        const double* p_init, int64_t n, double* p_out, double* rho4, uint8_t* status, int32_t* iters,
                        void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !kij || !temp || !z || !p_init || !status) return fail_msg("pcs_mix_bubble_dew: null required pointer");
+    if (int e = enter(n, params && kij && temp && z && p_init && status, "pcs_mix_bubble_dew: null required pointer"); e != GO_ON) return e;
     hipStream_t s = as_stream(stream);
     if (workspace) {
         // work-queue schedule: perm[n] + control block, pre-pass fugacities, init records and the robust list in the workspace
@@ -640,16 +619,12 @@ int pcs_mix_bubble_dew(int dew, const double* params, const double* kij, const d
         double* fug = reinterpret_cast<double*>(static_cast<char*>(workspace) + mix_ws_offset(n));
         double4* init = reinterpret_cast<double4*>(fug + 4 * n);
         int32_t* robust_list = reinterpret_cast<int32_t*>(fug + 8 * n);
-        if (int ez = zero_ints(ctrl, QCTRL_INTS, s)) return ez;
-        const unsigned g256 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(k_mix_class_count, dim3(g256), dim3(256), 0, s, params, n, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scan, dim3(1), dim3(64), 0, s, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scatter, dim3(g256), dim3(256), 0, s, params, n, ctrl, perm);
+        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
         if (dew)
             hipLaunchKernelGGL(k_mix_pure_fugacity, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, s, params, temp, n,
                                (const int32_t*)perm, fug);
         unsigned waves = (unsigned)queue_waves();
-        const unsigned needed = (unsigned)((n + 63) / 64);
+        const unsigned needed = grid_for(n, 64);
         if (waves > needed) waves = needed;
         if (dew) {
             hipLaunchKernelGGL(k_mix_init_queue<true>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n,
@@ -664,85 +639,54 @@ int pcs_mix_bubble_dew(int dew, const double* params, const double* kij, const d
                                (const int32_t*)perm, ctrl, (const double4*)init, (const int32_t*)robust_list, p_out, rho4, status,
                                iters);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail("k_mix_bubble_dew_queue launch", e);
-        return 0;
+        return launched("k_mix_bubble_dew_queue launch");
     }
-    const unsigned grid = (unsigned)((n + MBLOCK - 1) / MBLOCK);
+    const unsigned grid = grid_for(n, MBLOCK);
     if (dew)
         hipLaunchKernelGGL(k_mix_bubble_dew<true>, dim3(grid), dim3(MBLOCK), 0, s, params, kij, temp, z, p_init, n, p_out, rho4,
                            status, iters);
     else
         hipLaunchKernelGGL(k_mix_bubble_dew<false>, dim3(grid), dim3(MBLOCK), 0, s, params, kij, temp, z, p_init, n, p_out, rho4,
                            status, iters);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mix_bubble_dew launch", e);
-    return 0;
+    return launched("k_mix_bubble_dew launch");
 }
 
 int pcs_mix_derivatives(const double* params, const double* kij, const double* temp, const double* rho, int64_t n,
                         double* a, double* p, double* mu, double* v, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !kij || !temp || !rho) return fail_msg("pcs_mix_derivatives: null required pointer");
-    const unsigned grid = (unsigned)((n + MBLOCK - 1) / MBLOCK);
+    if (int e = enter(n, params && kij && temp && rho, "pcs_mix_derivatives: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, MBLOCK);
     hipLaunchKernelGGL(k_mix_derivatives, dim3(grid), dim3(MBLOCK), 0, as_stream(stream), params, kij,
                        temp, rho, n, a, p, mu, v);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mix_derivatives launch", e);
-    return 0;
+    return launched("k_mix_derivatives launch");
 }
 
 int pcs_mix_derivatives_vjp(const double* params, const double* kij, const double* temp, const double* rho, int64_t n,
                             const double* g_a, const double* g_p, const double* g_mu, const double* g_v, double* grad,
                             void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !kij || !temp || !rho || !grad) return fail_msg("pcs_mix_derivatives_vjp: null required pointer");
+    if (int e = enter(n, params && kij && temp && rho && grad, "pcs_mix_derivatives_vjp: null required pointer"); e != GO_ON) return e;
     hipStream_t s = as_stream(stream);
     const int32_t* order = nullptr;
     if (workspace) {
-        int32_t* perm = static_cast<int32_t*>(workspace);
-        int32_t* ctrl = perm + n;
-        if (int ez = zero_ints(ctrl, QCTRL_INTS, s)) return ez;
-        const unsigned g256 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(k_mix_class_count, dim3(g256), dim3(256), 0, s, params, n, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scan, dim3(1), dim3(64), 0, s, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scatter, dim3(g256), dim3(256), 0, s, params, n, ctrl, perm);
-        order = perm;
+        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
+        order = static_cast<const int32_t*>(workspace);
     }
-    hipLaunchKernelGGL(k_mix_derivatives_vjp, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, params, kij, temp, rho, n, g_a,
+    hipLaunchKernelGGL(k_mix_derivatives_vjp, dim3(grid_for(n, 64)), dim3(64), 0, s, params, kij, temp, rho, n, g_a,
                        g_p, g_mu, g_v, grad, order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mix_derivatives_vjp launch", e);
-    return 0;
+    return launched("k_mix_derivatives_vjp launch");
 }
 
 int pcs_mix_jacobian(int dew, const double* params, const double* kij, const double* temp, const double* rho4,
                      int64_t n, double* jac, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !kij || !temp || !rho4 || !jac) return fail_msg("pcs_mix_jacobian: null required pointer");
-    const unsigned grid = (unsigned)((n + MBLOCK - 1) / MBLOCK);
+    if (int e = enter(n, params && kij && temp && rho4 && jac, "pcs_mix_jacobian: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, MBLOCK);
     hipStream_t s = as_stream(stream);
     const int32_t* order = nullptr;
     if (workspace) {  // batch-wide class order (the permutation of the work-queue schedule)
-        int32_t* perm = static_cast<int32_t*>(workspace);
-        int32_t* ctrl = perm + n;
-        if (int ez = zero_ints(ctrl, QCTRL_INTS, s)) return ez;
-        const unsigned g256 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(k_mix_class_count, dim3(g256), dim3(256), 0, s, params, n, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scan, dim3(1), dim3(64), 0, s, ctrl);
-        hipLaunchKernelGGL(k_mix_class_scatter, dim3(g256), dim3(256), 0, s, params, n, ctrl, perm);
-        order = perm;
+        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
+        order = static_cast<const int32_t*>(workspace);
     }
     hipLaunchKernelGGL(k_mix_jacobian, dim3(grid), dim3(MBLOCK), 0, s, dew, params, kij, temp, rho4, n, jac, order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mix_jacobian launch", e);
-    return 0;
+    return launched("k_mix_jacobian launch");
 }
 
 }  // extern "C"

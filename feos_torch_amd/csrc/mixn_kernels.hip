@@ -353,7 +353,7 @@ int pcs_mixn_derivatives(const double* params, const double* temp, const double*
     if (ncomp < 1 || ncomp > 6) return fail_msg("pcs_mixn_derivatives: ncomp must be in [1, 6]");
     if (n == 0) return 0;
     if (!params || !temp || !rho) return fail_msg("pcs_mixn_derivatives: null required pointer");
-    const dim3 grid((unsigned)((n + NBLOCK - 1) / NBLOCK)), block(NBLOCK);
+    const dim3 grid(grid_for(n, NBLOCK)), block(NBLOCK);
     hipStream_t s = as_stream(stream);
     switch (ncomp) {
         case 1: hipLaunchKernelGGL(k_mixn_derivatives<1>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
@@ -363,9 +363,7 @@ int pcs_mixn_derivatives(const double* params, const double* temp, const double*
         case 5: hipLaunchKernelGGL(k_mixn_derivatives<5>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
         default: hipLaunchKernelGGL(k_mixn_derivatives<6>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mixn_derivatives launch", e);
-    return 0;
+    return launched("k_mixn_derivatives launch");
 }
 
 int pcs_mixn_derivatives_vjp(const double* params, const double* temp, const double* rho, int ncomp, int64_t n, const double* g_a,
@@ -375,7 +373,7 @@ int pcs_mixn_derivatives_vjp(const double* params, const double* temp, const dou
     if (ncomp < 1 || ncomp > 6) return fail_msg("pcs_mixn_derivatives_vjp: ncomp must be in [1, 6]");
     if (n == 0) return 0;
     if (!params || !temp || !rho || !grad) return fail_msg("pcs_mixn_derivatives_vjp: null required pointer");
-    const dim3 grid((unsigned)((n + NBLOCK - 1) / NBLOCK)), block(NBLOCK);
+    const dim3 grid(grid_for(n, NBLOCK)), block(NBLOCK);
     hipStream_t s = as_stream(stream);
     switch (ncomp) {
         case 1: hipLaunchKernelGGL(k_mixn_derivatives_vjp<1>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
@@ -385,9 +383,7 @@ int pcs_mixn_derivatives_vjp(const double* params, const double* temp, const dou
         case 5: hipLaunchKernelGGL(k_mixn_derivatives_vjp<5>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
         default: hipLaunchKernelGGL(k_mixn_derivatives_vjp<6>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mixn_derivatives_vjp launch", e);
-    return 0;
+    return launched("k_mixn_derivatives_vjp launch");
 }
 
 }  // extern "C"

@@ -92,33 +92,23 @@ extern "C" {
 
 int pcs_pure_critical_point(const double* params, const double* t_init, int64_t n, double* tc, double* pc, double* rhoc,
                             uint8_t* status, int32_t* iters, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !status) return fail_msg("pcs_pure_critical_point: null required pointer");
+    if (int e = enter(n, params && status, "pcs_pure_critical_point: null required pointer"); e != GO_ON) return e;
     if ((reinterpret_cast<uintptr_t>(params) & 15) != 0) return fail_msg("pcs_pure_critical_point: params must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_critical, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, t_init, n, tc, pc, rhoc, status,
                        iters);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_critical launch", e);
-    return 0;
+    return launched("k_pure_critical launch");
 }
 
 int pcs_pure_critical_point_vjp(const double* params, const double* tc, const double* rhoc, int64_t n, const double* g_tc,
                                 const double* g_pc, const double* g_rhoc, double* grad_params, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !tc || !rhoc || !grad_params) return fail_msg("pcs_pure_critical_point_vjp: null required pointer");
+    if (int e = enter(n, params && tc && rhoc && grad_params, "pcs_pure_critical_point_vjp: null required pointer"); e != GO_ON) return e;
     if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grad_params)) & 15) != 0)
         return fail_msg("pcs_pure_critical_point_vjp: params and grad_params must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_critical_vjp, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, tc, rhoc, n, g_tc, g_pc,
                        g_rhoc, grad_params);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_critical_vjp launch", e);
-    return 0;
+    return launched("k_pure_critical_vjp launch");
 }
 
 }  // extern "C"

@@ -572,8 +572,7 @@ PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float 
     return s.ok && s.done;
 }
 
-// fp32 pass, in two resumable parts so that a kernel can hand the few lanes that need more coupled iterations than their
-// wave-mates to another wave (k_pure_vle<true>: block-level straggler exchange):
+// fp32 pass, in two parts (vle_presolve_f32 below runs one after the other; nothing resumes a lane in between):
 //   presolve_begin:   zero-pressure liquid root, liquid state at it, virial-corrected ideal-gas vapour estimate
 //   presolve_coupled: coupled Newton towards the equal-area pressure from iteration s.it up to (excluding) it_end, or
 //                     until every lane of the wave is done
@@ -662,8 +661,8 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
     float pv_last = s.pv, dv_taken = s.dv_taken, ev = s.ev, sec_prev = s.sec_prev, d_prev = s.d_prev;
     bool lean_v = s.lean_v;
     int n_cpl = s.it;
-    // lanes of one wave may resume at different iteration numbers (straggler exchange): `it` below only bounds the loop,
-    // the lane's own count n_cpl decides what the first-iteration rule of the stop criterion sees
+    // `it` below only bounds the loop, the lane's own count n_cpl decides what the first-iteration rule of the stop
+    // criterion sees
     for (int it = 0; it < it_end; it++) {
         const bool act = !done && n_cpl < it_end;
         // Vapour evaluation.  A lane's first one computes a, a', a'' (pure_eval_f32).  From its second iteration on
@@ -721,7 +720,7 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
             }
             n_cpl++;
         }
-        // the liquid state follows every taken step (also the last one of this call: a resumed lane starts from it)
+        // the liquid state follows every taken step
         // the liquid barely moves after the first iteration: a lane whose liquid step was below 1e-3 carries its
         // liquid state to the new density by the Taylor expansion (a to 2nd, p to 1st order, dp kept) instead of a
         // re-evaluation; the error (~2.5 (dl/rho)^2 in the density) is below the fp32 noise the pass stops at.  The

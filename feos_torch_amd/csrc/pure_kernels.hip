@@ -14,6 +14,7 @@
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
+#include "block_order.hpp"
 #include "pure_solver.hpp"
 #include "pure_jacobian.hpp"
 
@@ -119,7 +120,8 @@ __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    // cooperative, coalesced staging (rows past n clamp to row n-1; never stored)
+    // cooperative, coalesced staging as stage_params, plus T (rows past n clamp to row n-1; never stored).  Written out,
+    // like the result stores below: behind a shared helper the compiler schedules these four kernels differently
     {
         const double2* src = reinterpret_cast<const double2*>(params);
         const int64_t last2 = n * 4 - 1;
@@ -135,24 +137,10 @@ __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
         }
         const int64_t g = row0 + t;
         lds[t * ROW_PAD + 8] = temp[g < n ? g : n - 1];
-        if (t < K1_BINS) bins[t] = 0;
+        block_order_reset<K1_BINS>(bins);
     }
     __syncthreads();
-    const int key = k1_bucket(&lds[t * ROW_PAD]);
-    atomicAdd(&bins[key], 1);
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-#pragma unroll
-        for (int b = 0; b < K1_BINS; b++) {
-            int c = bins[b];
-            bins[b] = acc;
-            acc += c;
-        }
-    }
-    __syncthreads();
-    perm[atomicAdd(&bins[key], 1)] = t;
-    __syncthreads();
+    block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
 
     const int r = perm[t];
     const int64_t i = row0 + r;
@@ -273,23 +261,9 @@ __global__ __launch_bounds__(BLOCK, K2_WAVES) void k_pure_liquid_density(const d
     __shared__ int perm[BLOCK];
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
-    if (t < K1_BINS) bins[t] = 0;
+    block_order_reset<K1_BINS>(bins);
     stage_params(params, n, row0, lds, par);
-    const int key = k1_bucket(&lds[t * ROW_PAD]);
-    atomicAdd(&bins[key], 1);
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-#pragma unroll
-        for (int b = 0; b < K1_BINS; b++) {
-            int c = bins[b];
-            bins[b] = acc;
-            acc += c;
-        }
-    }
-    __syncthreads();
-    perm[atomicAdd(&bins[key], 1)] = t;
-    __syncthreads();
+    block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
     const int src = perm[t];
 #pragma unroll
     for (int q = 0; q < 8; q++) par[q] = lds[src * ROW_PAD + q];
@@ -380,25 +354,11 @@ __global__ __launch_bounds__(BLOCK, K4_WAVES) void k_pure_jacobian(const double*
     __shared__ int perm[BUCKET ? BLOCK : 1];
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
-    if (BUCKET && t < K1_BINS) bins[t] = 0;
+    if (BUCKET) block_order_reset<K1_BINS>(bins);
     stage_params(params, n, row0, lds, par);
     int src = t;
     if (BUCKET) {
-        const int key = k1_bucket(&lds[t * ROW_PAD]);
-        atomicAdd(&bins[key], 1);
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-#pragma unroll
-            for (int b = 0; b < K1_BINS; b++) {
-                int c = bins[b];
-                bins[b] = acc;
-                acc += c;
-            }
-        }
-        __syncthreads();
-        perm[atomicAdd(&bins[key], 1)] = t;
-        __syncthreads();
+        block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
         src = perm[t];
 #pragma unroll
         for (int q = 0; q < 8; q++) par[q] = lds[src * ROW_PAD + q];
@@ -466,20 +426,16 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives_vjp(const double* __
 namespace pcs_abi {
 int launch_pure_vle_full(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq, double* rho_vl,
                          uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s) {
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_vle<false>, dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status, iters,
                        retry);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_vle launch", e);
-    return 0;
+    return launched("k_pure_vle launch");
 }
 int launch_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n, double* rho_out,
                                double* rho_root, uint8_t* status, hipStream_t s) {
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_liquid_density, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, n, rho_out, rho_root, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_liquid_density launch", e);
-    return 0;
+    return launched("k_pure_liquid_density launch");
 }
 }  // namespace pcs_abi
 #endif
@@ -501,8 +457,7 @@ static int launch_vle_fast(const double* params, const double* temp, int64_t n, 
                            double* rho_vl, uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s,
                            bool force_lite = false, bool all_fp64 = false) {
     if (int ez = zero_ints(retry, 1, s)) return ez;
-    hipError_t e;
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_for(n, BLOCK);
     // main kernel (lean: rows without an fp32 pre-solve go to the list with bit 31 set) + all-fp64 fallback kernel.
     //  * pressure only: k_pure_vle<true>, densities converged to ~1e-9 inside the kernel (enough for p*, whose error is of
     //    second order in them) and not handed out;
@@ -528,161 +483,113 @@ static int launch_vle_fast(const double* params, const double* temp, int64_t n, 
     }
     hipLaunchKernelGGL(k_pure_vle_fallback, dim3(FALLBACK_GRID), dim3(64), 0, s, params, temp, p_sat, rho_eq, rho_vl, status,
                        iters, retry, n);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_vle launch", e);
-    return 0;
+    return launched("k_pure_vle launch");
 }
 
-static int vle_args_ok(const double* params, const double* temp, int64_t n, const uint8_t* status,
-                       const void* workspace) {
-    if (int e = check_n(n)) return e;
-    if (n > 0 && (!params || !temp || !status || !workspace)) return fail_msg("pcs_pure_vle: null required pointer");
+// the pcs_pure_vle* family: stage 1 (fast kernel + fallback) and / or stage 2 (robust pass over the list in the workspace)
+enum : int { VLE_STAGE_FAST = 1, VLE_STAGE_RETRY = 2 };
+static int pure_vle_stages(int stages, const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
+                           double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream,
+                           bool force_lite = false, bool all_fp64 = false) {
+    if (int e = enter(n, params && temp && status && workspace, "pcs_pure_vle: null required pointer"); e != GO_ON) return e;
+    int32_t* retry = static_cast<int32_t*>(workspace);
+    hipStream_t s = as_stream(stream);
+    if (stages & VLE_STAGE_FAST)
+        if (int e = launch_vle_fast(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, s, force_lite, all_fp64)) return e;
+    if (stages & VLE_STAGE_RETRY) return launch_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters, retry, n, s);
     return 0;
 }
 
 int pcs_pure_vle(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                  double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = vle_args_ok(params, temp, n, status, workspace)) return e;
-    if (n == 0) return 0;
-    int32_t* retry = static_cast<int32_t*>(workspace);
-    if (int e = launch_vle_fast(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, as_stream(stream))) return e;
-    return launch_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters, retry, n, as_stream(stream));
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
 }
 
 int pcs_pure_vle_fp64(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                       double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = vle_args_ok(params, temp, n, status, workspace)) return e;
-    if (n == 0) return 0;
-    int32_t* retry = static_cast<int32_t*>(workspace);
-    if (int e = launch_vle_fast(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, as_stream(stream), false, true)) return e;
-    return launch_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters, retry, n, as_stream(stream));
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream,
+                           false, true);
 }
 
 int pcs_pure_vapor_pressure(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_vl,
                             uint8_t* status, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = vle_args_ok(params, temp, n, status, workspace)) return e;
-    if (n == 0) return 0;
-    int32_t* retry = static_cast<int32_t*>(workspace);
-    if (int e = launch_vle_fast(params, temp, n, p_sat, nullptr, rho_vl, status, nullptr, retry, as_stream(stream), true)) return e;
-    return launch_vle_retry(params, temp, p_sat, nullptr, rho_vl, status, nullptr, retry, n, as_stream(stream));
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, nullptr, rho_vl, status, nullptr, workspace, stream,
+                           true);
 }
 
 int pcs_pure_vle_fast(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                       double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = vle_args_ok(params, temp, n, status, workspace)) return e;
-    if (n == 0) return 0;
-    return launch_vle_fast(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, static_cast<int32_t*>(workspace),
-                           as_stream(stream));
+    return pure_vle_stages(VLE_STAGE_FAST, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
 }
 
 int pcs_pure_vle_retry(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                        double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = vle_args_ok(params, temp, n, status, workspace)) return e;
-    if (n == 0) return 0;
-    return launch_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters,
-                            static_cast<const int32_t*>(workspace), n, as_stream(stream));
+    return pure_vle_stages(VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
 }
 
 int pcs_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n,
                             double* rho_out, double* rho_root, uint8_t* status, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !pressure || !status) return fail_msg("pcs_pure_liquid_density: null required pointer");
+    if (int e = enter(n, params && temp && pressure && status, "pcs_pure_liquid_density: null required pointer"); e != GO_ON) return e;
     return launch_pure_liquid_density(params, temp, pressure, n, rho_out, rho_root, status, as_stream(stream));
 }
 
 int pcs_pure_derivatives(const double* params, const double* temp, const double* rho, int64_t n, double* a,
                          double* p, double* dp, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !rho) return fail_msg("pcs_pure_derivatives: null required pointer");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    if (int e = enter(n, params && temp && rho, "pcs_pure_derivatives: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_derivatives, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, temp, rho, n, a, p,
                        dp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_derivatives launch", e);
-    return 0;
+    return launched("k_pure_derivatives launch");
 }
 
 int pcs_pure_start_probe(const double* params, const double* temp, int64_t n, float* out, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !out) return fail_msg("pcs_pure_start_probe: null required pointer");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    if (int e = enter(n, params && temp && out, "pcs_pure_start_probe: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_start_probe, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, temp, n, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_start_probe launch", e);
-    return 0;
+    return launched("k_pure_start_probe launch");
 }
 
 int pcs_pure_derivatives_vjp(const double* params, const double* temp, const double* rho, int64_t n, const double* g_a,
                              const double* g_p, const double* g_dp, double* grad_params, double* grad_temp, double* grad_rho,
                              void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !rho) return fail_msg("pcs_pure_derivatives_vjp: null required pointer");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    if (int e = enter(n, params && temp && rho, "pcs_pure_derivatives_vjp: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, BLOCK);
     hipLaunchKernelGGL(k_pure_derivatives_vjp, dim3(grid), dim3(BLOCK), 0, as_stream(stream), params, temp, rho, n, g_a, g_p,
                        g_dp, grad_params, grad_temp, grad_rho);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_derivatives_vjp launch", e);
-    return 0;
+    return launched("k_pure_derivatives_vjp launch");
+}
+
+// both Jacobian entry points: `entry` names the caller in the messages; jac or (gout, grad_*) select the output form
+static int launch_pure_jacobian(const char* entry, int which, const double* params, const double* temp, const double* pressure,
+                                const double* rho_vl, int64_t n, double* jac, const double* gout, double* grad_params,
+                                double* grad_temp, double* grad_pressure, hipStream_t s) {
+    const int polish = (which & PCS_JAC_POLISH) ? 1 : 0;
+    which &= ~PCS_JAC_POLISH;
+    if (which == 1 && !pressure) return fail_msg(entry, "pressure required for liquid_density");
+    if ((reinterpret_cast<uintptr_t>(grad_params) & 15) != 0) return fail_msg(entry, "grad_params must be 16-byte aligned");
+    const unsigned grid = grid_for(n, BLOCK);
+    switch (which) {
+        case 0: hipLaunchKernelGGL(k_pure_jacobian<0>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
+        case 1: hipLaunchKernelGGL(k_pure_jacobian<1>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
+        case 2: hipLaunchKernelGGL(k_pure_jacobian<2>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
+        default: return fail_msg(entry, "which must be 0, 1 or 2");
+    }
+    return launched("k_pure_jacobian launch");
 }
 
 int pcs_pure_jacobian(int which, const double* params, const double* temp, const double* pressure,
                       const double* rho_vl, int64_t n, double* jac, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !rho_vl || !jac) return fail_msg("pcs_pure_jacobian: null required pointer");
-    const int polish = (which & PCS_JAC_POLISH) ? 1 : 0;
-    which &= ~PCS_JAC_POLISH;
-    if (which == 1 && !pressure) return fail_msg("pcs_pure_jacobian: pressure required for liquid_density");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipStream_t s = as_stream(stream);
-    switch (which) {
-        case 0: hipLaunchKernelGGL(k_pure_jacobian<0>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, nullptr, nullptr, nullptr, nullptr, polish); break;
-        case 1: hipLaunchKernelGGL(k_pure_jacobian<1>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, nullptr, nullptr, nullptr, nullptr, polish); break;
-        case 2: hipLaunchKernelGGL(k_pure_jacobian<2>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, nullptr, nullptr, nullptr, nullptr, polish); break;
-        default: return fail_msg("pcs_pure_jacobian: which must be 0, 1 or 2");
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_jacobian launch", e);
-    return 0;
+    if (int e = enter(n, params && temp && rho_vl && jac, "pcs_pure_jacobian: null required pointer"); e != GO_ON) return e;
+    return launch_pure_jacobian("pcs_pure_jacobian", which, params, temp, pressure, rho_vl, n, jac, nullptr, nullptr, nullptr, nullptr,
+                                as_stream(stream));
 }
 
 int pcs_pure_jacobian_vjp(int which, const double* params, const double* temp, const double* pressure, const double* rho_vl,
                           const double* gout, int64_t n, double* grad_params, double* grad_temp, double* grad_pressure,
                           void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !temp || !rho_vl || !gout) return fail_msg("pcs_pure_jacobian_vjp: null required pointer");
-    const int polish = (which & PCS_JAC_POLISH) ? 1 : 0;
-    which &= ~PCS_JAC_POLISH;
-    if (which == 1 && !pressure) return fail_msg("pcs_pure_jacobian_vjp: pressure required for liquid_density");
-    if ((reinterpret_cast<uintptr_t>(grad_params) & 15) != 0) return fail_msg("pcs_pure_jacobian_vjp: grad_params must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipStream_t s = as_stream(stream);
-    double* none = nullptr;
-    switch (which) {
-        case 0: hipLaunchKernelGGL(k_pure_jacobian<0>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, none, gout, grad_params, grad_temp, grad_pressure, polish); break;
-        case 1: hipLaunchKernelGGL(k_pure_jacobian<1>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, none, gout, grad_params, grad_temp, grad_pressure, polish); break;
-        case 2: hipLaunchKernelGGL(k_pure_jacobian<2>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, none, gout, grad_params, grad_temp, grad_pressure, polish); break;
-        default: return fail_msg("pcs_pure_jacobian_vjp: which must be 0, 1 or 2");
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_jacobian launch", e);
-    return 0;
+    if (int e = enter(n, params && temp && rho_vl && gout, "pcs_pure_jacobian_vjp: null required pointer"); e != GO_ON) return e;
+    return launch_pure_jacobian("pcs_pure_jacobian_vjp", which, params, temp, pressure, rho_vl, n, nullptr, gout, grad_params, grad_temp,
+                                grad_pressure, as_stream(stream));
 }
 
 }  // extern "C"

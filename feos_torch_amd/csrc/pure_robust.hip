@@ -65,9 +65,7 @@ int launch_pure_vle_retry(const double* params, const double* temp, double* p_sa
                           uint8_t* status, int32_t* iters, const int32_t* retry, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_pure_vle_robust, dim3(RETRY_GRID), dim3(64), 0, s, params, temp, p_sat, rho_eq, rho_vl, status,
                        iters, retry, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_pure_vle_robust launch", e);
-    return 0;
+    return launched("k_pure_vle_robust launch");
 }
 
 }  // namespace pcs_abi

@@ -304,8 +304,7 @@ PCS_DEV int vle_fast(const double* par, double T, VleResult& out, double tol_l =
 // steers the step (error ~1e-3 of a ~1e-6 step); the residuals and p* are fp64.  Lanes without a usable fp32
 // result return ST_FALLBACK (the all-fp64 path runs on them in a separate small kernel, which keeps this one at
 // 122 VGPRs / four waves per SIMD), lanes that fail afterwards ST_RETRY (robust pass).
-// vle_fast_lite = fp32 pre-solve (pure_f32.hpp) + vle_lite_finish; k_pure_vle<true> runs the two parts itself with the
-// block-level straggler exchange in between.
+// vle_fast_lite = fp32 pre-solve (vle_presolve_f32, pure_f32.hpp) + vle_lite_finish.
 // POLISH (densities requested: equilibrium_liquid_density, rho_vl for the Jacobians): one more update of both densities
 // with the exact dp/drho of an fp64 D2 evaluation at the converged state -- the iteration above leaves them at ~1e-9
 // (linear convergence with the fp32 slope), the exact Newton step squares that.  p* then carries the exact second-order term.

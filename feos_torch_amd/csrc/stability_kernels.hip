@@ -6,6 +6,7 @@
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
+#include "block_order.hpp"
 #include "gc_kernel_common.hpp"
 #include "mix_kernel_common.hpp"
 #include "stability.hpp"
@@ -34,24 +35,8 @@ __global__ __launch_bounds__(SBLOCK) void k_mix_stability(const double* __restri
     __shared__ int bins[MIX_BINS + 1];
     const int t = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * SBLOCK;
-    if (t <= MIX_BINS) bins[t] = 0;
-    __syncthreads();
-    int key = MIX_BINS;  // rows past n sort last
-    if (row0 + t < n) key = mix_bucket(params + 16 * (row0 + t));
-    atomicAdd(&bins[key], 1);
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-#pragma unroll
-        for (int b = 0; b <= MIX_BINS; b++) {
-            int c = bins[b];
-            bins[b] = acc;
-            acc += c;
-        }
-    }
-    __syncthreads();
-    perm[atomicAdd(&bins[key], 1)] = t;
-    __syncthreads();
+    // rows past n sort last, in a bucket of their own
+    block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
     const int64_t i = row0 + perm[t];
     if (i >= n) return;
     double par[16], k0, k1;
@@ -91,16 +76,11 @@ extern "C" {
 
 int pcs_mix_stability(const double* params, const double* kij, const double* temp, const double* rho, int64_t n, double* tpd,
                       double* rho_trial, uint8_t* status, void* stream) {
-    g_err[0] = 0;
-    if (int e = check_n(n)) return e;
-    if (n == 0) return 0;
-    if (!params || !kij || !temp || !rho || !status) return fail_msg("pcs_mix_stability: null required pointer");
-    const unsigned grid = (unsigned)((n + SBLOCK - 1) / SBLOCK);
+    if (int e = enter(n, params && kij && temp && rho && status, "pcs_mix_stability: null required pointer"); e != GO_ON) return e;
+    const unsigned grid = grid_for(n, SBLOCK);
     hipLaunchKernelGGL(k_mix_stability, dim3(grid), dim3(SBLOCK), 0, as_stream(stream), params, kij, temp, rho, n, tpd, rho_trial,
                        status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_mix_stability launch", e);
-    return 0;
+    return launched("k_mix_stability launch");
 }
 
 int pcs_gc_stability(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp, const double* rho,
@@ -110,12 +90,10 @@ int pcs_gc_stability(const double* table, int S, const uint8_t* rows, const doub
     if (n == 0) return 0;
     if (!table || !rows || !phi || !temp || !rho || !status) return fail_msg("pcs_gc_stability: null required pointer");
     if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_stability: rows must be 16-byte aligned");
-    const unsigned grid = (unsigned)((n + SBLOCK - 1) / SBLOCK);
+    const unsigned grid = grid_for(n, SBLOCK);
     hipLaunchKernelGGL(k_gc_stability, dim3(grid), dim3(SBLOCK), gc_lds_bytes(S, SBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES),
                        as_stream(stream), table, S, rows, phi, temp, rho, n, tpd, rho_trial, status, order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_gc_stability launch", e);
-    return 0;
+    return launched("k_gc_stability launch");
 }
 
 }  // extern "C"

@@ -46,51 +46,68 @@ def _same_rows(n, **named):
             raise ValueError(f"{name} has {t.shape[0]} rows, expected {n}")
 
 
+def _device_of(x):
+    """The device of a GPU tensor, else the current GPU (host inputs are copied there by _prep)."""
+    return x.device if isinstance(x, torch.Tensor) and x.is_cuda else _dev()
+
+
+def _check_order(order, n, device):
+    if order is not None and (order.dtype != torch.int32 or order.shape != (n,) or order.device != device or not order.is_contiguous()):
+        raise ValueError("order must be a contiguous int32 tensor [n] on the device of the table")
+
+
+def _call(device, name, *args):
+    """One C-ABI call on `device`: tensors and None become pointers, the current stream is appended, a non-zero return
+    code raises PcsError with the library's message."""
+    with torch.cuda.device(device):
+        rc = getattr(_lib.lib(), name)(*[_lib.ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args],
+                                       _lib.current_stream_ptr(device))
+    _lib.check(rc, name)
+
+
+def _workspace(n, device, mix=False):
+    """int32 workspace of pcs_workspace_bytes(n) (mix: pcs_mix_workspace_bytes)"""
+    L = _lib.lib()
+    nbytes = L.pcs_mix_workspace_bytes(n) if mix else L.pcs_workspace_bytes(n)
+    return torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=device)
+
+
 def pure_vle(params, temperature, want_p=True, want_rho_eq=False, want_iters=False, want_rho_vl=True, all_fp64=False):
     """Pure VLE on the GPU.  -> dict(p_sat [Pa], rho_eq [kmol/m3], rho_vl [n,2] A^-3, status bool, iters).
     want_rho_vl=False with want_rho_eq=False selects the pressure-only kernel (fp64 finish with the fp32
     pre-solve's dp/drho; densities not returned); rho_vl: the all-fp64 kernel; rho_eq: pressure-only kernel + one exact fp64
     Newton update of the densities.
     all_fp64: the validation twin (pcs_pure_vle_fp64: fp64 second derivatives in every iteration)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     temperature = _prep(temperature, device)
     n = temperature.shape[0]
     if params.shape[0] != n:
         raise ValueError("parameters and temperature differ in length")
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        p_sat = torch.empty(n, dtype=_F64, device=device) if want_p else None
-        rho_eq = torch.empty(n, dtype=_F64, device=device) if want_rho_eq else None
-        rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
-        ws = torch.empty(max(1, L.pcs_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        fn = L.pcs_pure_vle_fp64 if all_fp64 else L.pcs_pure_vle
-        rc = fn(_lib.ptr(params), _lib.ptr(temperature), n, _lib.ptr(p_sat), _lib.ptr(rho_eq),
-                _lib.ptr(rho_vl), _lib.ptr(status), _lib.ptr(iters), _lib.ptr(ws),
-                _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_vle")
+    p_sat = torch.empty(n, dtype=_F64, device=device) if want_p else None
+    rho_eq = torch.empty(n, dtype=_F64, device=device) if want_rho_eq else None
+    rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    ws = _workspace(n, device)
+    _call(device, "pcs_pure_vle_fp64" if all_fp64 else "pcs_pure_vle", params, temperature, n, p_sat, rho_eq, rho_vl,
+          status, iters, ws)
     return {"p_sat": p_sat, "rho_eq": rho_eq, "rho_vl": rho_vl, "status": status.view(torch.bool), "iters": iters}
 
 
 def pure_vapor_pressure(params, temperature, want_rho_vl=False):
     """PcSaftPure.vapor_pressure in one call (pcs_pure_vapor_pressure): always the pressure-only kernel, so p_sat has the
     same bits with and without the densities.  -> dict(p_sat [Pa], rho_vl [n,2] A^-3 or None, status bool)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     temperature = _prep(temperature, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        p_sat = torch.empty(n, dtype=_F64, device=device)
-        rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        ws = torch.empty(max(1, L.pcs_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        rc = L.pcs_pure_vapor_pressure(_lib.ptr(params), _lib.ptr(temperature), n, _lib.ptr(p_sat), _lib.ptr(rho_vl),
-                                       _lib.ptr(status), _lib.ptr(ws), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_vapor_pressure")
+    p_sat = torch.empty(n, dtype=_F64, device=device)
+    rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    ws = _workspace(n, device)
+    _call(device, "pcs_pure_vapor_pressure", params, temperature, n, p_sat, rho_vl, status, ws)
     return {"p_sat": p_sat, "rho_eq": None, "rho_vl": rho_vl, "status": status.view(torch.bool), "iters": None}
 
 
@@ -203,41 +220,32 @@ def compact_rows(comp, x):
 
 def pure_liquid_density(params, temperature, pressure):
     """-> dict(rho [kmol/m3], rho_root [A^-3], status bool)"""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     temperature = _prep(temperature, device)
     pressure = _prep(pressure, device)
     n = temperature.shape[0]
     if params.shape[0] != n or pressure.shape[0] != n:
         raise ValueError("parameters, temperature and pressure differ in length")
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        rho = torch.empty(n, dtype=_F64, device=device)
-        root = torch.empty(n, dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        rc = L.pcs_pure_liquid_density(_lib.ptr(params), _lib.ptr(temperature), _lib.ptr(pressure), n,
-                                       _lib.ptr(rho), _lib.ptr(root), _lib.ptr(status),
-                                       _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_liquid_density")
+    rho = torch.empty(n, dtype=_F64, device=device)
+    root = torch.empty(n, dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    _call(device, "pcs_pure_liquid_density", params, temperature, pressure, n, rho, root, status)
     return {"rho": rho, "rho_root": root, "status": status.view(torch.bool)}
 
 
 def pure_derivatives(params, temperature, density):
     """(a, p, dp) reduced — PcSaftPure.derivatives (feos_torch/pcsaft_pure.py:180-182)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     temperature = _prep(temperature, device)
     density = _prep(density, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        a = torch.empty(n, dtype=_F64, device=device)
-        p = torch.empty(n, dtype=_F64, device=device)
-        dp = torch.empty(n, dtype=_F64, device=device)
-        rc = L.pcs_pure_derivatives(_lib.ptr(params), _lib.ptr(temperature), _lib.ptr(density), n, _lib.ptr(a),
-                                    _lib.ptr(p), _lib.ptr(dp), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_derivatives")
+    a = torch.empty(n, dtype=_F64, device=device)
+    p = torch.empty(n, dtype=_F64, device=device)
+    dp = torch.empty(n, dtype=_F64, device=device)
+    _call(device, "pcs_pure_derivatives", params, temperature, density, n, a, p, dp)
     return a, p, dp
 
 
@@ -257,12 +265,9 @@ def pure_jacobian(which, params, temperature, pressure, rho_vl, polish=False):
     rho_vl = _prep(rho_vl, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, pressure=pressure, rho_vl=rho_vl)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        jac = torch.empty((n, 10), dtype=_F64, device=device)
-        rc = L.pcs_pure_jacobian(_WHICH[which] | (JAC_POLISH if polish else 0), _lib.ptr(params), _lib.ptr(temperature), _lib.ptr(pressure),
-                                 _lib.ptr(rho_vl), n, _lib.ptr(jac), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_jacobian")
+    jac = torch.empty((n, 10), dtype=_F64, device=device)
+    _call(device, "pcs_pure_jacobian", _WHICH[which] | (JAC_POLISH if polish else 0), params, temperature, pressure,
+          rho_vl, n, jac)
     return jac
 
 
@@ -277,41 +282,34 @@ def pure_jacobian_vjp(which, params, temperature, pressure, rho_vl, gout, need=(
     gout = _prep(gout, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, pressure=pressure, rho_vl=rho_vl, gout=gout)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        gp = torch.empty((n, 8), dtype=_F64, device=device) if need[0] else None
-        gt = torch.empty(n, dtype=_F64, device=device) if need[1] else None
-        gpr = torch.empty(n, dtype=_F64, device=device) if (need[2] and pressure is not None) else None
-        rc = L.pcs_pure_jacobian_vjp(_WHICH[which] | (JAC_POLISH if polish else 0), _lib.ptr(params), _lib.ptr(temperature), _lib.ptr(pressure), _lib.ptr(rho_vl),
-                                     _lib.ptr(gout), n, _lib.ptr(gp), _lib.ptr(gt), _lib.ptr(gpr), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_jacobian_vjp")
+    gp = torch.empty((n, 8), dtype=_F64, device=device) if need[0] else None
+    gt = torch.empty(n, dtype=_F64, device=device) if need[1] else None
+    gpr = torch.empty(n, dtype=_F64, device=device) if (need[2] and pressure is not None) else None
+    _call(device, "pcs_pure_jacobian_vjp", _WHICH[which] | (JAC_POLISH if polish else 0), params, temperature, pressure,
+          rho_vl, gout, n, gp, gt, gpr)
     return gp, gt, gpr
 
 
 def pure_critical_point(params, initial_temperature=None, want_iters=False):
     """Critical point of every parameter row (pcs_pure_critical_point).
     -> dict(t_c [K], p_c [Pa], rho_c [kmol/m3], status bool (True = failed), iters int32 or None)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     t_init = None if initial_temperature is None else _prep(initial_temperature, device)
     n = params.shape[0]
     _same_rows(n, initial_temperature=t_init)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        tc = torch.empty(n, dtype=_F64, device=device)
-        pc = torch.empty(n, dtype=_F64, device=device)
-        rhoc = torch.empty(n, dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
-        rc = L.pcs_pure_critical_point(_lib.ptr(params), _lib.ptr(t_init), n, _lib.ptr(tc), _lib.ptr(pc), _lib.ptr(rhoc),
-                                       _lib.ptr(status), _lib.ptr(iters), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_critical_point")
+    tc = torch.empty(n, dtype=_F64, device=device)
+    pc = torch.empty(n, dtype=_F64, device=device)
+    rhoc = torch.empty(n, dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    _call(device, "pcs_pure_critical_point", params, t_init, n, tc, pc, rhoc, status, iters)
     return {"t_c": tc, "p_c": pc, "rho_c": rhoc, "status": status.view(torch.bool), "iters": iters}
 
 
 def pure_critical_point_vjp(params, t_c, rho_c, g_tc=None, g_pc=None, g_rhoc=None):
     """Backward pass of pure_critical_point on converged rows: grad_params [n,8] (pcs_pure_critical_point_vjp)."""
-    device = t_c.device if isinstance(t_c, torch.Tensor) and t_c.is_cuda else _dev()
+    device = _device_of(t_c)
     params = _prep(params, device, (8,))
     t_c = _prep(t_c, device)
     rho_c = _prep(rho_c, device)
@@ -320,12 +318,8 @@ def pure_critical_point_vjp(params, t_c, rho_c, g_tc=None, g_pc=None, g_rhoc=Non
     g_rhoc = None if g_rhoc is None else _prep(g_rhoc, device)
     n = t_c.shape[0]
     _same_rows(n, parameters=params, rho_c=rho_c, g_tc=g_tc, g_pc=g_pc, g_rhoc=g_rhoc)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        gp = torch.empty((n, 8), dtype=_F64, device=device)
-        rc = L.pcs_pure_critical_point_vjp(_lib.ptr(params), _lib.ptr(t_c), _lib.ptr(rho_c), n, _lib.ptr(g_tc), _lib.ptr(g_pc),
-                                           _lib.ptr(g_rhoc), _lib.ptr(gp), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_critical_point_vjp")
+    gp = torch.empty((n, 8), dtype=_F64, device=device)
+    _call(device, "pcs_pure_critical_point_vjp", params, t_c, rho_c, n, g_tc, g_pc, g_rhoc, gp)
     return gp
 
 
@@ -412,7 +406,7 @@ class PureVlePlan:
 def mix_bubble_dew(params, kij, temperature, molefracs, pressure, dew, want_iters=False):
     """Bubble (dew=False) / dew (dew=True) points.  -> dict(p [Pa], rho4 [n,4] A^-3 = (rhoV_1, rhoV_2,
     rhoL_1, rhoL_2), status bool, iters)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (2, 8))
     kij = _prep(kij, device, (2,))
     temperature = _prep(temperature, device)
@@ -421,38 +415,30 @@ def mix_bubble_dew(params, kij, temperature, molefracs, pressure, dew, want_iter
     n = temperature.shape[0]
     if not (params.shape[0] == kij.shape[0] == molefracs.shape[0] == pressure.shape[0] == n):
         raise ValueError("inputs differ in length")
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        p = torch.empty(n, dtype=_F64, device=device)
-        rho4 = torch.empty((n, 4), dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
-        ws = torch.empty(max(1, L.pcs_mix_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        rc = L.pcs_mix_bubble_dew(int(bool(dew)), _lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature),
-                                  _lib.ptr(molefracs), _lib.ptr(pressure), n, _lib.ptr(p), _lib.ptr(rho4),
-                                  _lib.ptr(status), _lib.ptr(iters), _lib.ptr(ws), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mix_bubble_dew")
+    p = torch.empty(n, dtype=_F64, device=device)
+    rho4 = torch.empty((n, 4), dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    ws = _workspace(n, device, mix=True)
+    _call(device, "pcs_mix_bubble_dew", int(bool(dew)), params, kij, temperature, molefracs, pressure, n, p, rho4, status,
+          iters, ws)
     return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
 
 
 def mix_derivatives(params, kij, temperature, density):
     """(a [n], p [n], mu [n,2], v [n,2]) — PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (2, 8))
     kij = _prep(kij, device, (2,))
     temperature = _prep(temperature, device)
     density = _prep(density, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, density=density)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        a = torch.empty(n, dtype=_F64, device=device)
-        p = torch.empty(n, dtype=_F64, device=device)
-        mu = torch.empty((n, 2), dtype=_F64, device=device)
-        v = torch.empty((n, 2), dtype=_F64, device=device)
-        rc = L.pcs_mix_derivatives(_lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature), _lib.ptr(density), n,
-                                   _lib.ptr(a), _lib.ptr(p), _lib.ptr(mu), _lib.ptr(v), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mix_derivatives")
+    a = torch.empty(n, dtype=_F64, device=device)
+    p = torch.empty(n, dtype=_F64, device=device)
+    mu = torch.empty((n, 2), dtype=_F64, device=device)
+    v = torch.empty((n, 2), dtype=_F64, device=device)
+    _call(device, "pcs_mix_derivatives", params, kij, temperature, density, n, a, p, mu, v)
     return a, p, mu, v
 
 
@@ -460,21 +446,17 @@ def mix_stability(params, kij, temperature, density):
     """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
     density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,
     3 invalid feed)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (2, 8))
     kij = _prep(kij, device, (2,))
     temperature = _prep(temperature, device)
     density = _prep(density, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, density=density)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        tpd = torch.empty(n, dtype=_F64, device=device)
-        rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        rc = L.pcs_mix_stability(_lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature), _lib.ptr(density), n, _lib.ptr(tpd),
-                                 _lib.ptr(rho_trial), _lib.ptr(status), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mix_stability")
+    tpd = torch.empty(n, dtype=_F64, device=device)
+    rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    _call(device, "pcs_mix_stability", params, kij, temperature, density, n, tpd, rho_trial, status)
     return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
 
 
@@ -510,13 +492,9 @@ def mix_jacobian(params, kij, temperature, rho4, dew):
     rho4 = _prep(rho4, device, (4,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, rho4=rho4)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        jac = torch.empty((n, 19), dtype=_F64, device=device)
-        ws = torch.empty(max(1, L.pcs_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        rc = L.pcs_mix_jacobian(int(bool(dew)), _lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature),
-                                _lib.ptr(rho4), n, _lib.ptr(jac), _lib.ptr(ws), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mix_jacobian")
+    jac = torch.empty((n, 19), dtype=_F64, device=device)
+    ws = _workspace(n, device)
+    _call(device, "pcs_mix_jacobian", int(bool(dew)), params, kij, temperature, rho4, n, jac, ws)
     return jac
 
 
@@ -577,20 +555,14 @@ def gc_bubble_dew(table, S, rows, phi, temperature, molefracs, pressure, dew, wa
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, molefracs=molefracs, pressure=pressure)
-    if order is not None and (order.dtype != torch.int32 or order.shape != (n,) or order.device != device or not order.is_contiguous()):
-        raise ValueError("order must be a contiguous int32 tensor [n] on the device of the table")
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        p = torch.empty(n, dtype=_F64, device=device)
-        rho4 = torch.empty((n, 4), dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
-        ws = torch.empty(max(1, L.pcs_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        rc = L.pcs_gc_bubble_dew(int(bool(dew)), _lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi),
-                                 _lib.ptr(temperature), _lib.ptr(molefracs), _lib.ptr(pressure), n, _lib.ptr(p),
-                                 _lib.ptr(rho4), _lib.ptr(status), _lib.ptr(iters), _lib.ptr(order), _lib.ptr(ws),
-                                 _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_bubble_dew")
+    _check_order(order, n, device)
+    p = torch.empty(n, dtype=_F64, device=device)
+    rho4 = torch.empty((n, 4), dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    ws = _workspace(n, device)
+    _call(device, "pcs_gc_bubble_dew", int(bool(dew)), table, int(S), rows, phi, temperature, molefracs, pressure, n, p,
+          rho4, status, iters, order, ws)
     return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
 
 
@@ -602,16 +574,11 @@ def gc_derivatives(table, S, rows, phi, temperature, density):
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        a = torch.empty(n, dtype=_F64, device=device)
-        p = torch.empty(n, dtype=_F64, device=device)
-        mu = torch.empty((n, 2), dtype=_F64, device=device)
-        v = torch.empty((n, 2), dtype=_F64, device=device)
-        rc = L.pcs_gc_derivatives(_lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi), _lib.ptr(temperature),
-                                  _lib.ptr(density), n, _lib.ptr(a), _lib.ptr(p), _lib.ptr(mu), _lib.ptr(v),
-                                  _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_derivatives")
+    a = torch.empty(n, dtype=_F64, device=device)
+    p = torch.empty(n, dtype=_F64, device=device)
+    mu = torch.empty((n, 2), dtype=_F64, device=device)
+    v = torch.empty((n, 2), dtype=_F64, device=device)
+    _call(device, "pcs_gc_derivatives", table, int(S), rows, phi, temperature, density, n, a, p, mu, v)
     return a, p, mu, v
 
 
@@ -625,17 +592,11 @@ def gc_stability(table, S, rows, phi, temperature, density, order=None):
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density)
-    if order is not None and (order.dtype != torch.int32 or order.shape != (n,) or order.device != device or not order.is_contiguous()):
-        raise ValueError("order must be a contiguous int32 tensor [n] on the device of the table")
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        tpd = torch.empty(n, dtype=_F64, device=device)
-        rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
-        status = torch.empty(n, dtype=torch.uint8, device=device)
-        rc = L.pcs_gc_stability(_lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi), _lib.ptr(temperature), _lib.ptr(density),
-                                n, _lib.ptr(tpd), _lib.ptr(rho_trial), _lib.ptr(status), _lib.ptr(order),
-                                _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_stability")
+    _check_order(order, n, device)
+    tpd = torch.empty(n, dtype=_F64, device=device)
+    rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
+    status = torch.empty(n, dtype=torch.uint8, device=device)
+    _call(device, "pcs_gc_stability", table, int(S), rows, phi, temperature, density, n, tpd, rho_trial, status, order)
     return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
 
 
@@ -648,15 +609,10 @@ def gc_jacobian(table, S, rows, phi, temperature, rho4, dew, order=None):
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, rho4=rho4)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        jac = torch.empty((n, 7), dtype=_F64, device=device)
-        agg = torch.empty((n, 6), dtype=_F64, device=device)
-        rc = L.pcs_gc_jacobian(int(bool(dew)), _lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi),
-                               _lib.ptr(temperature), _lib.ptr(rho4), n, _lib.ptr(jac), _lib.ptr(agg),
-                               _lib.ptr(order) if order is not None and order.shape[0] == n else None,
-                               _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_jacobian")
+    jac = torch.empty((n, 7), dtype=_F64, device=device)
+    agg = torch.empty((n, 6), dtype=_F64, device=device)
+    _call(device, "pcs_gc_jacobian", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, jac, agg,
+          order if order is not None and order.shape[0] == n else None)
     return jac, agg
 
 
@@ -670,14 +626,9 @@ def gc_segment_gradient(table, S, rows, phi, temperature, rho4, dew, gout=None, 
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, rho4=rho4, gout=gout)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        grad = torch.zeros((int(S), 8), dtype=_F64, device=device)
-        rc = L.pcs_gc_segment_gradient(int(bool(dew)), _lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi),
-                                       _lib.ptr(temperature), _lib.ptr(rho4), n, _lib.ptr(gout), _lib.ptr(grad),
-                                       _lib.ptr(order) if order is not None and order.shape[0] == n else None,
-                                       _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_segment_gradient")
+    grad = torch.zeros((int(S), 8), dtype=_F64, device=device)
+    _call(device, "pcs_gc_segment_gradient", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, gout, grad,
+          order if order is not None and order.shape[0] == n else None)
     return grad
 
 
@@ -687,41 +638,31 @@ def _opt(x, device, shape_tail=None):
 
 def pure_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_dp=None):
     """Backward of PcSaftPure.derivatives: -> (grad_params [n,8], grad_T [n], grad_rho [n])."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (8,))
     temperature, density = _prep(temperature, device), _prep(density, device)
     g_a, g_p, g_dp = _opt(g_a, device), _opt(g_p, device), _opt(g_dp, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density, g_a=g_a, g_p=g_p, g_dp=g_dp)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        gpar = torch.empty((n, 8), dtype=_F64, device=device)
-        gT = torch.empty(n, dtype=_F64, device=device)
-        grho = torch.empty(n, dtype=_F64, device=device)
-        rc = L.pcs_pure_derivatives_vjp(_lib.ptr(params), _lib.ptr(temperature), _lib.ptr(density), n, _lib.ptr(g_a),
-                                        _lib.ptr(g_p), _lib.ptr(g_dp), _lib.ptr(gpar), _lib.ptr(gT), _lib.ptr(grho),
-                                        _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_pure_derivatives_vjp")
+    gpar = torch.empty((n, 8), dtype=_F64, device=device)
+    gT = torch.empty(n, dtype=_F64, device=device)
+    grho = torch.empty(n, dtype=_F64, device=device)
+    _call(device, "pcs_pure_derivatives_vjp", params, temperature, density, n, g_a, g_p, g_dp, gpar, gT, grho)
     return gpar, gT, grho
 
 
 def mix_derivatives_vjp(params, kij, temperature, density, g_a=None, g_p=None, g_mu=None, g_v=None):
     """Backward of PcSaftMix.derivatives: -> grad [n,21] = dL/d(16 parameters, kij0, kij1, T, rho_0, rho_1)."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     params = _prep(params, device, (2, 8))
     kij = _prep(kij, device, (2,))
     temperature, density = _prep(temperature, device), _prep(density, device, (2,))
     g_a, g_p, g_mu, g_v = _opt(g_a, device), _opt(g_p, device), _opt(g_mu, device, (2,)), _opt(g_v, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        grad = torch.empty((n, 21), dtype=_F64, device=device)
-        ws = torch.empty(max(1, L.pcs_workspace_bytes(n) // 4), dtype=torch.int32, device=device)
-        rc = L.pcs_mix_derivatives_vjp(_lib.ptr(params), _lib.ptr(kij), _lib.ptr(temperature), _lib.ptr(density), n,
-                                       _lib.ptr(g_a), _lib.ptr(g_p), _lib.ptr(g_mu), _lib.ptr(g_v), _lib.ptr(grad),
-                                       _lib.ptr(ws), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mix_derivatives_vjp")
+    grad = torch.empty((n, 21), dtype=_F64, device=device)
+    ws = _workspace(n, device)
+    _call(device, "pcs_mix_derivatives_vjp", params, kij, temperature, density, n, g_a, g_p, g_mu, g_v, grad, ws)
     return grad
 
 
@@ -734,23 +675,17 @@ def gc_derivatives_vjp(table, S, rows, phi, temperature, density, g_a=None, g_p=
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        gseg = torch.zeros((int(S), 8), dtype=_F64, device=device)
-        jac9 = torch.empty((n, 9), dtype=_F64, device=device)
-        agg = torch.empty((n, 6), dtype=_F64, device=device)
-        rc = L.pcs_gc_derivatives_vjp(_lib.ptr(table), int(S), _lib.ptr(rows), _lib.ptr(phi), _lib.ptr(temperature),
-                                      _lib.ptr(density), n, _lib.ptr(g_a), _lib.ptr(g_p), _lib.ptr(g_mu), _lib.ptr(g_v),
-                                      _lib.ptr(gseg), _lib.ptr(jac9), _lib.ptr(agg),
-                                      _lib.ptr(order) if order is not None and order.shape[0] == n else None,
-                                      _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_gc_derivatives_vjp")
+    gseg = torch.zeros((int(S), 8), dtype=_F64, device=device)
+    jac9 = torch.empty((n, 9), dtype=_F64, device=device)
+    agg = torch.empty((n, 6), dtype=_F64, device=device)
+    _call(device, "pcs_gc_derivatives_vjp", table, int(S), rows, phi, temperature, density, n, g_a, g_p, g_mu, g_v, gseg,
+          jac9, agg, order if order is not None and order.shape[0] == n else None)
     return gseg, jac9, agg
 
 
 def mixn_derivatives(params, temperature, density):
     """n-component PcSaftMix.derivatives without k_ij: params [n, nc, 8], density [n, nc] -> (a [n], p [n], mu [n,nc], v [n,nc])."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     if params.dim() != 3 or params.shape[2] != 8 or not 1 <= params.shape[1] <= 6:
         raise ValueError("parameters must have shape [N, n, 8] with 1 <= n <= 6 components")
     nc = int(params.shape[1])
@@ -759,21 +694,17 @@ def mixn_derivatives(params, temperature, density):
     density = _prep(density, device, (nc,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        a = torch.empty(n, dtype=_F64, device=device)
-        p = torch.empty(n, dtype=_F64, device=device)
-        mu = torch.empty((n, nc), dtype=_F64, device=device)
-        v = torch.empty((n, nc), dtype=_F64, device=device)
-        rc = L.pcs_mixn_derivatives(_lib.ptr(params), _lib.ptr(temperature), _lib.ptr(density), nc, n, _lib.ptr(a), _lib.ptr(p),
-                                    _lib.ptr(mu), _lib.ptr(v), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mixn_derivatives")
+    a = torch.empty(n, dtype=_F64, device=device)
+    p = torch.empty(n, dtype=_F64, device=device)
+    mu = torch.empty((n, nc), dtype=_F64, device=device)
+    v = torch.empty((n, nc), dtype=_F64, device=device)
+    _call(device, "pcs_mixn_derivatives", params, temperature, density, nc, n, a, p, mu, v)
     return a, p, mu, v
 
 
 def mixn_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_mu=None, g_v=None):
     """Backward of the n-component derivatives: grad [n, 9 nc + 1] = dL/d(parameters [nc][8], T, rho [nc])."""
-    device = params.device if isinstance(params, torch.Tensor) and params.is_cuda else _dev()
+    device = _device_of(params)
     nc = int(params.shape[1])
     params = _prep(params, device, (nc, 8))
     temperature = _prep(temperature, device)
@@ -781,10 +712,6 @@ def mixn_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_mu=
     g_a, g_p, g_mu, g_v = _opt(g_a, device), _opt(g_p, device), _opt(g_mu, device, (nc,)), _opt(g_v, device, (nc,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    L = _lib.lib()
-    with torch.cuda.device(device):
-        grad = torch.empty((n, 9 * nc + 1), dtype=_F64, device=device)
-        rc = L.pcs_mixn_derivatives_vjp(_lib.ptr(params), _lib.ptr(temperature), _lib.ptr(density), nc, n, _lib.ptr(g_a), _lib.ptr(g_p),
-                                        _lib.ptr(g_mu), _lib.ptr(g_v), _lib.ptr(grad), _lib.current_stream_ptr(device))
-        _lib.check(rc, "pcs_mixn_derivatives_vjp")
+    grad = torch.empty((n, 9 * nc + 1), dtype=_F64, device=device)
+    _call(device, "pcs_mixn_derivatives_vjp", params, temperature, density, nc, n, g_a, g_p, g_mu, g_v, grad)
     return grad
