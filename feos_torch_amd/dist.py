@@ -23,7 +23,7 @@ def init_from_env():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     use_cuda = torch.cuda.is_available()
-    # rehearsal on a 1-GPU box: PCS_SINGLE_DEVICE=1 maps every rank to cuda:0 (use with PCS_DIST_BACKEND=gloo,
+    # rehearsal on a 1-GPU machine: PCS_SINGLE_DEVICE=1 maps every rank to cuda:0 (use with PCS_DIST_BACKEND=gloo,
     # RCCL refuses two ranks on one device)
     if os.environ.get("PCS_SINGLE_DEVICE") == "1":
         local = 0
@@ -31,7 +31,7 @@ def init_from_env():
     if use_cuda:
         torch.cuda.set_device(device)
     # PCS_FORCE_DIST=1: initialise the process group at world size 1 too, so that the collectives below really run on the
-    # backend (RCCL on a one-GPU box: bench.py --force-gather, tests/test_rccl_gpu.py)
+    # backend (RCCL on a one-GPU machine: bench.py --force-gather, tests/test_rccl_gpu.py)
     if (world > 1 or os.environ.get("PCS_FORCE_DIST") == "1") and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
@@ -66,7 +66,7 @@ def gather_rows(local, n_total, group=None, force=False):
     """All-gather 1-D (or [rows, k]) shards that were cut with shard_bounds() back into the
     full-length tensor, on every rank.  Shards are padded to the largest shard so the
     collective has a static message size.  At world size 1 the shard is the result and no
-    collective runs unless `force` (exercises the backend on a one-GPU box)."""
+    collective runs unless `force` (exercises the backend on a one-GPU machine)."""
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not force):
         return local
     world = dist.get_world_size(group)

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import native
+from . import _shell, native
+from .native import _detached
 
 MAXE = 8  # distinct segment types / bond types per molecule in the 80-byte row encoding
 
@@ -152,6 +153,8 @@ class _GcDerivatives(torch.autograd.Function):
     """(a, p, mu, v) = derivatives(...) with gradients to k_ab, phi, temperature, density and the eight segment parameter
     vectors (feos_torch/gc_pcsaft.py:116-253, :443-468 are torch graphs in the reference)."""
 
+    COLUMNS = ((6, 1, (-1,)), (7, 2, (-1, 2)))  # temperature, density in jac9 [n,9]
+
     @staticmethod
     def forward(ctx, model, kab, phi, temperature, density, *segment_parameters):
         dev = model.device
@@ -159,113 +162,92 @@ class _GcDerivatives(torch.autograd.Function):
         ph = native._prep(phi, dev, (2,))
         T = native._prep(temperature, dev)
         rho = native._prep(density, dev, (2,))
-        a, p, mu, v = native.gc_derivatives(table, model.S, model.rows, ph, T, rho)
-        ctx.save_for_backward(table, model.rows, ph, T, rho)
-        ctx.set_materialize_grads(False)
         ctx.S = model.S
-        ctx.devs = (kab.device, phi.device, temperature.device, density.device)
-        ctx.seg_devs = [q.device for q in segment_parameters]
-        out = phi.device
-        return a.to(out), p.to(out), mu.to(out), v.to(out)
+        return _shell.save_state(ctx, (phi, kab, temperature, density, *segment_parameters), (table, model.rows, ph, T, rho),
+                                 native.gc_derivatives(table, model.S, model.rows, ph, T, rho))
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_a, g_p, g_mu, g_v):
+    def backward(ctx, *grads):
+        need, devs = ctx.needs_input_grad, ctx.in_devices  # devs: phi, kab, temperature, density, segment parameters
+        if all(g is None for g in grads):
+            return (None,) * len(need)
         table, rows, ph, T, rho = ctx.saved_tensors
-        nseg = len(ctx.seg_devs)
-        if g_a is None and g_p is None and g_mu is None and g_v is None:
-            return (None,) * (5 + nseg)
-        S = ctx.S
-        gseg, jac9, agg = native.gc_derivatives_vjp(table, S, rows, ph, T, rho, g_a, g_p, g_mu, g_v)
-        need = ctx.needs_input_grad
-        gk = _kab_gradient(table, S, rows, ph, T, jac9[:, 1], jac9[:, 4]).to(ctx.devs[0]) if need[1] else None
-        gphi = _phi_gradient(jac9, agg, ph).to(ctx.devs[1]) if need[2] else None
-        gT = jac9[:, 6].contiguous().to(ctx.devs[2]) if need[3] else None
-        grho = jac9[:, 7:9].contiguous().to(ctx.devs[3]) if need[4] else None
-        gs = [gseg[:, k].to(ctx.seg_devs[k]) if need[5 + k] else None for k in range(nseg)]
-        return (None, gk, gphi, gT, grho, *gs)
+        gseg, jac9, agg = native.gc_derivatives_vjp(table, ctx.S, rows, ph, T, rho, *grads)
+        gk = _kab_gradient(table, ctx.S, rows, ph, T, jac9[:, 1], jac9[:, 4]).to(devs[1]) if need[1] else None
+        gphi = _phi_gradient(jac9, agg, ph).to(devs[0]) if need[2] else None
+        gs = [gseg[:, k].to(dev) if nd else None for k, (dev, nd) in enumerate(zip(devs[4:], need[5:]))]
+        return (None, gk, gphi, *_shell.split(jac9, _GcDerivatives.COLUMNS, need[3:5], devs[2:4]), *gs)
 
 
 class _GcBubbleDew(torch.autograd.Function):
-    """value[n_ok], nans[n].  Dense solve, one compaction plan (its 4-byte row count is the call's only host synchronisation),
-    single-kernel gathers only when rows were dropped (native.Compaction; the reference drops them inside the native call,
-    src/gc_pcsaft.rs:103-171)."""
+    """value[n_ok], nans[n][, stable[n_ok]], plan.  Dense solve, one compaction plan (its 4-byte row count is the call's only
+    host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the reference drops them
+    inside the native call, src/gc_pcsaft.rs:103-171)."""
 
     @staticmethod
-    def forward(ctx, dew, model, kab, phi, temperature, molefracs, pressure, box, check, *segment_parameters):
-        dev = model.device
+    def forward(ctx, dew, model, kab, phi, temperature, molefracs, pressure, check, *segment_parameters):
+        dev, S = model.device, model.S
         table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
         ph = native._prep(phi, dev, (2,))
         T = native._prep(temperature, dev)
-        r = native.gc_bubble_dew(table, model.S, model.rows, ph, T, native._prep(molefracs, dev),
-                                 native._prep(pressure, dev), dew, order=model._class_order(table))
-        nans = r["status"]
-        comp = native.Compaction(nans)
-        box.append(comp)
+        r = native.gc_bubble_dew(table, S, model.rows, ph, T, native._prep(molefracs, dev), native._prep(pressure, dev), dew,
+                                 order=model._class_order(table))
+        comp = native.Compaction(r["status"])
         value = comp.gather(r["p"])
-        needs = [ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]]
-        seg_needs = list(ctx.needs_input_grad[9:])
-        ctx.saved = False
-        if any(needs) or any(seg_needs):
-            rows_ok, ph_ok, T_ok, rho4_ok = comp.gather(model.rows), comp.gather(ph), comp.gather(T), comp.gather(r["rho4"])
-            # the class order belongs to the uncompacted rows: used when every row converged
-            order = model._class_order(table) if comp.all_ok else None
-            if any(needs):
-                jac, agg = native.gc_jacobian(table, model.S, rows_ok, ph_ok, T_ok, rho4_ok, dew, order=order)
-            else:
-                jac = agg = T.new_empty(0)
-            ctx.save_for_backward(jac, agg, rows_ok, ph_ok, T_ok, table, rho4_ok if any(seg_needs) else T.new_empty(0),
-                                  order if (order is not None and any(seg_needs)) else nans.new_empty(0))
+        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, temperature
+        ctx.seg_needs = list(ctx.needs_input_grad[8:])
+        # the class order belongs to the uncompacted rows: used when every row converged
+        order = model._class_order(table) if comp.all_ok else None
+        ctx.comp = None
+        if any(ctx.needs) or any(ctx.seg_needs):
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": comp.gather(T)}
+            rho4_ok = comp.gather(r["rho4"])
+            if any(ctx.needs):  # per-row Jacobians for k_ab, phi and T
+                keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], keep["T"], rho4_ok, dew, order=order)
+            if any(ctx.seg_needs):  # the segment gradient runs in backward, at the densities
+                keep["rho4"] = rho4_ok
+                if order is not None:
+                    keep["order"] = order
+            ctx.kept = tuple(keep)  # what was saved, by name
+            ctx.save_for_backward(*keep.values())
             ctx.comp = comp
-            ctx.saved = True
-        ctx.needs = needs
-        ctx.seg_needs = seg_needs
-        ctx.dew = bool(dew)
-        ctx.seg_devs = [p.device if isinstance(p, torch.Tensor) else None for p in segment_parameters]
-        ctx.S = model.S
+        ctx.dew, ctx.S = bool(dew), S
+        ctx.seg_devs = [p.device for p in segment_parameters]
         ctx.devs = (kab.device, phi.device, temperature.device)
-        out_device = phi.device
-        nans = nans.to(out_device)
+        flags = ()
         if check:
-            # stability of the specified phase at the converged solution (liquid for bubble, vapour for dew), on the
-            # compacted rows: aligned with `value`
-            rho4 = comp.gather(r["rho4"])
-            st = native.gc_stability(table, model.S, comp.gather(model.rows), comp.gather(ph), comp.gather(T),
-                                     rho4[:, 0:2] if dew else rho4[:, 2:4],
-                                     order=model._class_order(table) if comp.all_ok else None)["status"]
-            stable = (st == 0).to(out_device)
-            ctx.mark_non_differentiable(nans, stable)
-            return value.to(out_device), nans, stable
-        ctx.mark_non_differentiable(nans)
-        return value.to(out_device), nans
+            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.gc_stability(
+                table, S, comp.gather(model.rows), comp.gather(ph), comp.gather(T), feed, order=order)),)
+        return (*_shell.finish(ctx, phi.device, [value], r["status"], *flags), comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, _g, *_g_stable):
+    def backward(ctx, g_value, *_g_flags):
         nseg = len(ctx.seg_needs)
-        if not ctx.saved:  # nothing the pressure depends on required a gradient
-            return (None,) * (9 + nseg)
-        jac, agg, rows, ph, T, table, rho4, order = ctx.saved_tensors
         comp, S = ctx.comp, ctx.S
+        if comp is None:  # nothing the pressure depends on required a gradient
+            return (None,) * (8 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T, jac = kept["table"], kept["rows"], kept["ph"], kept["T"], kept.get("jac")
         g = g_value.to(table.device).contiguous()
         gk = gphi = gT = None
         if ctx.needs[0]:
             gk = _kab_gradient(table, S, rows, ph, T, g * jac[:, 1], g * jac[:, 4]).to(ctx.devs[0])
         if ctx.needs[1]:
-            gphi = comp.expand(_phi_gradient(jac, agg, ph), g).to(ctx.devs[1])
+            gphi = comp.expand(_phi_gradient(jac, kept["agg"], ph), g).to(ctx.devs[1])
         if ctx.needs[2]:
             gT = comp.expand(jac, g, 6, 1).view(comp.n).to(ctx.devs[2])
         gseg = [None] * nseg
         if any(ctx.seg_needs):
             # the whole table in one kernel: sum_i g_i dp_i/d seg[S,8] (the segment-parameter gradient is lazy: it needs
             # the upstream gradient, so unlike the per-row Jacobians above it runs here, not in forward)
-            G = native.gc_segment_gradient(table, S, rows, ph, T, rho4, ctx.dew, gout=g,
-                                           order=order if order.numel() == rows.shape[0] else None)
+            G = native.gc_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout=g, order=kept.get("order"))
             gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
-        return (None, None, gk, gphi, gT, None, None, None, None, *gseg)
+        return (None, None, gk, gphi, gT, None, None, None, *gseg)
 
 
-class GcPcSaftMix:
+class GcPcSaftMix(_shell.Reducible):
     def __init__(self, segment_identifier, parameter, segment_lists, bond_lists, binary_segment_records, phi=None):
         """Arguments as the reference (feos_torch/gc_pcsaft.py:14-22): segment identifiers [S], the
         8 segment parameter vectors (m, sigma, epsilon_k, mu, kappa_ab, epsilon_k_ab, na, nb), per-row
@@ -277,7 +259,7 @@ class GcPcSaftMix:
         self.S = len(self.segment_identifier)
         if self.S > 32:
             raise ValueError("at most 32 segment types per table")
-        self.device = _device_of(phi, *parameter)
+        self.device = _first_gpu(phi, *parameter)
         # the caller's tensors stay attached to the model: they are inputs of the autograd Function of every property
         self._segment_parameters = tuple(p if isinstance(p, torch.Tensor) else torch.as_tensor(p, dtype=torch.float64)
                                          for p in parameter)
@@ -294,12 +276,7 @@ class GcPcSaftMix:
             if bool((cnt > 1).any()):
                 raise Exception("Only up to one associating segment per component is allowed!")
         self._order = None  # class order of the rows, see _class_order
-        idx = {s: i for i, s in enumerate(self.segment_identifier)}
-        # symmetric k_ab matrix built exactly as the reference does (:60-63), keeps autograd history
-        self.kab = torch.zeros((self.S, self.S), dtype=torch.float64)
-        for s1, s2, k in binary_segment_records:
-            self.kab[idx[s1], idx[s2]] = k
-            self.kab[idx[s2], idx[s1]] = k
+        self.kab = _kab_matrix(self.segment_identifier, binary_segment_records)  # keeps autograd history
         self.phi = torch.ones((n, 2), dtype=torch.float64) if phi is None else phi
         self.gc_pcsaft = GcPcSaft._from_model(self)
 
@@ -326,12 +303,11 @@ class GcPcSaftMix:
         return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
 
     def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
-        box = []
         # mole fractions and initial pressure do not enter the reference's final formula (:483-490): no gradient flows to them
-        out = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure), box,
-                                 bool(check_stability), *self._segment_parameters)
-        self._reduce(box[0])
-        return out
+        *out, comp = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure),
+                                        bool(check_stability), *self._segment_parameters)
+        self._reduce(comp)
+        return tuple(out)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction
@@ -345,34 +321,40 @@ class GcPcSaftMix:
 
     def _class_order(self, table):
         """Class order of the model's rows for the kernels' schedule (native.gc_class_order): computed on first use and
-        again after `reduce` — the rows are fixed in between."""
+        again after `reduce` — the rows are fixed in between.  (GcPcSaft borrows this method.)"""
         if self._order is None or self._order.shape[0] != self.rows.shape[0]:
             self._order = native.gc_class_order(table, self.S, self.rows)
         return self._order
 
-    def _reduce(self, comp):
+    def _reduce(self, comp):  # `reduce(nans)` (:514-528) is _shell.Reducible's
         if comp.all_ok:
             return
         self.rows = comp.gather(self.rows)
         self.phi = native.compact_rows(comp, self.phi)
         self._order = None
 
-    def reduce(self, nans):
-        """Drop failed rows from the model (:514-528)."""
-        self._reduce(native.Compaction(nans.to(self.device)))
+    def _compute_device(self):
+        return self.device
 
 
-def _device_of(*tensors):
+def _kab_matrix(identifier, binary_segment_records, value=lambda k: k):
+    """Symmetric [S,S] k_ab matrix built exactly as the reference does (feos_torch/gc_pcsaft.py:60-63): on the CPU, entry by
+    entry, so that tensor entries of the records keep their autograd history."""
+    idx = {s: i for i, s in enumerate(identifier)}
+    kab = torch.zeros((len(identifier), len(identifier)), dtype=torch.float64)
+    for s1, s2, k in binary_segment_records:
+        kab[idx[s1], idx[s2]] = value(k)
+        kab[idx[s2], idx[s1]] = value(k)
+    return kab
+
+
+def _first_gpu(*tensors):
     """The GPU a gc model computes on: the device of the first CUDA tensor among its inputs (phi, segment parameters), else the
     current GPU -- not a device pinned at import or construction time of some other model."""
     for t in tensors:
         if isinstance(t, torch.Tensor) and t.is_cuda:
             return t.device
     return native._dev()
-
-
-def _detached(x):
-    return x.detach() if isinstance(x, torch.Tensor) else x
 
 
 class GcPcSaft:
@@ -384,15 +366,10 @@ class GcPcSaft:
         ident = [s for s, _ in segment_records]
         par = np.stack([np.asarray(v, dtype=np.float64) for _, v in segment_records], axis=0)
         self.S = len(ident)
-        self.device = _device_of(phi)
+        self.device = _first_gpu(phi)
         self.seg = torch.from_numpy(par).contiguous()
         self.rows = encode_rows_device(ident, segments, bonds, self.device)
-        kab = torch.zeros((self.S, self.S), dtype=torch.float64)
-        idx = {s: i for i, s in enumerate(ident)}
-        for s1, s2, k in binary_segment_records:
-            kab[idx[s1], idx[s2]] = float(k)
-            kab[idx[s2], idx[s1]] = float(k)
-        self.table = build_table(self.seg.to(self.device), kab.to(self.device))
+        self.table = build_table(self.seg.to(self.device), _kab_matrix(ident, binary_segment_records, float).to(self.device))
         self.phi = torch.as_tensor(np.asarray(phi, dtype=np.float64))
         self._order = None
 
@@ -407,10 +384,8 @@ class GcPcSaft:
 
     def _solve(self, temperature, molefracs, pressure, dew):
         t, x, p = (native._as_f64(v, 1) for v in (temperature, molefracs, pressure))
-        if self._order is None or self._order.shape[0] != self.rows.shape[0]:
-            self._order = native.gc_class_order(self.table, self.S, self.rows)
         r = native.gc_bubble_dew(self.table, self.S, self.rows, self.phi, torch.from_numpy(t), torch.from_numpy(x),
-                                 torch.from_numpy(p), dew, order=self._order)
+                                 torch.from_numpy(p), dew, order=GcPcSaftMix._class_order(self, self.table))
         return native.Compaction(r["status"]).gather(r["rho4"]).cpu().numpy(), r["status"].cpu().numpy()
 
     def bubble_point(self, temperature, liquid_molefracs, pressure):

@@ -65,11 +65,30 @@ def _call(device, name, *args):
     _lib.check(rc, name)
 
 
+def _detached(x):
+    return x.detach() if isinstance(x, torch.Tensor) else x
+
+
+def _order_or_none(order, n):
+    """A class order of another length than the batch (it belongs to the uncompacted rows) is not used."""
+    return order if order is not None and order.shape[0] == n else None
+
+
+def _new(device, shape, dtype=_F64):
+    """Uninitialised output on `device`; shape: a row count or a tuple."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _news(device, *shapes):
+    """One uninitialised float64 output per shape."""
+    return [torch.empty(shape, dtype=_F64, device=device) for shape in shapes]
+
+
 def _workspace(n, device, mix=False):
     """int32 workspace of pcs_workspace_bytes(n) (mix: pcs_mix_workspace_bytes)"""
     L = _lib.lib()
     nbytes = L.pcs_mix_workspace_bytes(n) if mix else L.pcs_workspace_bytes(n)
-    return torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=device)
+    return _new(device, max(1, nbytes // 4), dtype=torch.int32)
 
 
 def pure_vle(params, temperature, want_p=True, want_rho_eq=False, want_iters=False, want_rho_vl=True, all_fp64=False):
@@ -84,11 +103,11 @@ def pure_vle(params, temperature, want_p=True, want_rho_eq=False, want_iters=Fal
     n = temperature.shape[0]
     if params.shape[0] != n:
         raise ValueError("parameters and temperature differ in length")
-    p_sat = torch.empty(n, dtype=_F64, device=device) if want_p else None
-    rho_eq = torch.empty(n, dtype=_F64, device=device) if want_rho_eq else None
-    rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
-    status = torch.empty(n, dtype=torch.uint8, device=device)
-    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    p_sat = _new(device, n) if want_p else None
+    rho_eq = _new(device, n) if want_rho_eq else None
+    rho_vl = _new(device, (n, 2)) if want_rho_vl else None
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
     ws = _workspace(n, device)
     _call(device, "pcs_pure_vle_fp64" if all_fp64 else "pcs_pure_vle", params, temperature, n, p_sat, rho_eq, rho_vl,
           status, iters, ws)
@@ -103,9 +122,9 @@ def pure_vapor_pressure(params, temperature, want_rho_vl=False):
     temperature = _prep(temperature, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params)
-    p_sat = torch.empty(n, dtype=_F64, device=device)
-    rho_vl = torch.empty((n, 2), dtype=_F64, device=device) if want_rho_vl else None
-    status = torch.empty(n, dtype=torch.uint8, device=device)
+    p_sat = _new(device, n)
+    rho_vl = _new(device, (n, 2)) if want_rho_vl else None
+    status = _new(device, n, dtype=torch.uint8)
     ws = _workspace(n, device)
     _call(device, "pcs_pure_vapor_pressure", params, temperature, n, p_sat, rho_vl, status, ws)
     return {"p_sat": p_sat, "rho_eq": None, "rho_vl": rho_vl, "status": status.view(torch.bool), "iters": None}
@@ -125,11 +144,8 @@ class Compaction:
         self.status = status.contiguous()
         self.n = int(status.shape[0])
         self.device = status.device
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            self.cws = torch.empty(max(1, L.pcs_compact_workspace_bytes(self.n) // 4), dtype=torch.int32, device=self.device)
-            _lib.check(L.pcs_compact_plan(_lib.ptr(self.status), self.n, _lib.ptr(self.cws),
-                                          _lib.current_stream_ptr(self.device)), "pcs_compact_plan")
+        self.cws = _new(self.device, max(1, _lib.lib().pcs_compact_workspace_bytes(self.n) // 4), dtype=torch.int32)
+        _call(self.device, "pcs_compact_plan", self.status, self.n, self.cws)
         self.n_ok = int(self.cws[0].item()) if self.n else 0
         self.all_ok = self.n_ok == self.n
 
@@ -151,22 +167,16 @@ class Compaction:
         width = 1
         for d in tail:
             width *= int(d)
-        out = torch.empty((self.n_ok,) + tail, dtype=_F64, device=self.device)
+        out = _new(self.device, (self.n_ok,) + tail)
         if self.n_ok and width:
-            L = _lib.lib()
-            with torch.cuda.device(self.device):
-                _lib.check(L.pcs_compact_rows(_lib.ptr(self.status), self.n, _lib.ptr(self.cws), _lib.ptr(x), width,
-                                              _lib.ptr(out), None, _lib.current_stream_ptr(self.device)), "pcs_compact_rows")
+            _call(self.device, "pcs_compact_rows", self.status, self.n, self.cws, x, width, out, None)
         return out
 
     def index(self):
         """int32 [n_ok]: original row of every kept row."""
-        out = torch.empty(self.n_ok, dtype=torch.int32, device=self.device)
+        out = _new(self.device, self.n_ok, dtype=torch.int32)
         if self.n_ok:
-            L = _lib.lib()
-            with torch.cuda.device(self.device):
-                _lib.check(L.pcs_compact_rows(_lib.ptr(self.status), self.n, _lib.ptr(self.cws), None, 1, None, _lib.ptr(out),
-                                              _lib.current_stream_ptr(self.device)), "pcs_compact_rows")
+            _call(self.device, "pcs_compact_rows", self.status, self.n, self.cws, None, 1, None, out)
         return out
 
     def expand(self, src, g=None, col0=0, ncol=None):
@@ -183,13 +193,10 @@ class Compaction:
         if self.n_ok == 0:  # nothing kept: all zeros (an empty tensor has no data pointer to hand to the kernel)
             out = torch.zeros((self.n, ncol), dtype=_F64, device=self.device)
             return out.view(self.n) if (one_d and ncol == 1) else out
-        out = torch.empty((self.n, ncol), dtype=_F64, device=self.device)
+        out = _new(self.device, (self.n, ncol))
         if self.n:
-            L = _lib.lib()
-            with torch.cuda.device(self.device):
-                _lib.check(L.pcs_expand_rows(None if self.all_ok else _lib.ptr(self.status), self.n, _lib.ptr(self.cws),
-                                             None if g is None else _lib.ptr(g.contiguous()), _lib.ptr(src2), stride, col0, ncol,
-                                             _lib.ptr(out), _lib.current_stream_ptr(self.device)), "pcs_expand_rows")
+            _call(self.device, "pcs_expand_rows", None if self.all_ok else self.status, self.n, self.cws,
+                  None if g is None else g.contiguous(), src2, stride, col0, ncol, out)
         return out.view(self.n) if (one_d and ncol == 1) else out
 
 
@@ -227,9 +234,8 @@ def pure_liquid_density(params, temperature, pressure):
     n = temperature.shape[0]
     if params.shape[0] != n or pressure.shape[0] != n:
         raise ValueError("parameters, temperature and pressure differ in length")
-    rho = torch.empty(n, dtype=_F64, device=device)
-    root = torch.empty(n, dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
+    rho, root = _news(device, n, n)
+    status = _new(device, n, dtype=torch.uint8)
     _call(device, "pcs_pure_liquid_density", params, temperature, pressure, n, rho, root, status)
     return {"rho": rho, "rho_root": root, "status": status.view(torch.bool)}
 
@@ -242,9 +248,7 @@ def pure_derivatives(params, temperature, density):
     density = _prep(density, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density)
-    a = torch.empty(n, dtype=_F64, device=device)
-    p = torch.empty(n, dtype=_F64, device=device)
-    dp = torch.empty(n, dtype=_F64, device=device)
+    a, p, dp = _news(device, n, n, n)
     _call(device, "pcs_pure_derivatives", params, temperature, density, n, a, p, dp)
     return a, p, dp
 
@@ -265,7 +269,7 @@ def pure_jacobian(which, params, temperature, pressure, rho_vl, polish=False):
     rho_vl = _prep(rho_vl, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, pressure=pressure, rho_vl=rho_vl)
-    jac = torch.empty((n, 10), dtype=_F64, device=device)
+    jac = _new(device, (n, 10))
     _call(device, "pcs_pure_jacobian", _WHICH[which] | (JAC_POLISH if polish else 0), params, temperature, pressure,
           rho_vl, n, jac)
     return jac
@@ -282,9 +286,9 @@ def pure_jacobian_vjp(which, params, temperature, pressure, rho_vl, gout, need=(
     gout = _prep(gout, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, pressure=pressure, rho_vl=rho_vl, gout=gout)
-    gp = torch.empty((n, 8), dtype=_F64, device=device) if need[0] else None
-    gt = torch.empty(n, dtype=_F64, device=device) if need[1] else None
-    gpr = torch.empty(n, dtype=_F64, device=device) if (need[2] and pressure is not None) else None
+    gp = _new(device, (n, 8)) if need[0] else None
+    gt = _new(device, n) if need[1] else None
+    gpr = _new(device, n) if (need[2] and pressure is not None) else None
     _call(device, "pcs_pure_jacobian_vjp", _WHICH[which] | (JAC_POLISH if polish else 0), params, temperature, pressure,
           rho_vl, gout, n, gp, gt, gpr)
     return gp, gt, gpr
@@ -298,11 +302,9 @@ def pure_critical_point(params, initial_temperature=None, want_iters=False):
     t_init = None if initial_temperature is None else _prep(initial_temperature, device)
     n = params.shape[0]
     _same_rows(n, initial_temperature=t_init)
-    tc = torch.empty(n, dtype=_F64, device=device)
-    pc = torch.empty(n, dtype=_F64, device=device)
-    rhoc = torch.empty(n, dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
-    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    tc, pc, rhoc = _news(device, n, n, n)
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
     _call(device, "pcs_pure_critical_point", params, t_init, n, tc, pc, rhoc, status, iters)
     return {"t_c": tc, "p_c": pc, "rho_c": rhoc, "status": status.view(torch.bool), "iters": iters}
 
@@ -318,9 +320,118 @@ def pure_critical_point_vjp(params, t_c, rho_c, g_tc=None, g_pc=None, g_rhoc=Non
     g_rhoc = None if g_rhoc is None else _prep(g_rhoc, device)
     n = t_c.shape[0]
     _same_rows(n, parameters=params, rho_c=rho_c, g_tc=g_tc, g_pc=g_pc, g_rhoc=g_rhoc)
-    gp = torch.empty((n, 8), dtype=_F64, device=device)
+    gp = _new(device, (n, 8))
     _call(device, "pcs_pure_critical_point_vjp", params, t_c, rho_c, n, g_tc, g_pc, g_rhoc, gp)
     return gp
+
+
+def _as_f64(x, ndim):
+    x = np.asarray(x)
+    if x.dtype != np.float64:
+        raise TypeError(f"argument must be a float64 array, got {x.dtype}")  # PyReadonlyArray<f64>
+    if x.ndim != ndim:
+        raise TypeError(f"argument must be {ndim}-dimensional, got {x.ndim}")
+    return np.ascontiguousarray(x)
+
+
+class PureVlePlan:
+    """Pre-allocated launch plan for repeated pure-VLE solves on a fixed number of rows: all
+    outputs and the retry workspace are allocated once; ``run`` only enqueues kernels on the
+    current HIP stream (no allocation, no host synchronisation), so steps can be timed with
+    HIP events."""
+
+    def __init__(self, n, device, want_rho_eq=False, want_rho_vl=False, all_fp64=False):
+        self.all_fp64 = bool(all_fp64)
+        self.n = int(n)
+        self.device = torch.device(device)
+        self.p_sat = _new(self.device, self.n)
+        self.rho_eq = _new(self.device, self.n) if want_rho_eq else None
+        self.rho_vl = _new(self.device, (self.n, 2)) if want_rho_vl else None
+        self.status = _new(self.device, self.n, dtype=torch.uint8)
+        self.ws = _workspace(self.n, self.device)
+
+    def _run(self, name, params, temperature):
+        _call(self.device, name, params, temperature, self.n, self.p_sat, self.rho_eq, self.rho_vl, self.status, None, self.ws)
+
+    def run(self, params, temperature):
+        self._run("pcs_pure_vle_fp64" if self.all_fp64 else "pcs_pure_vle", params, temperature)
+
+    def run_fast(self, params, temperature):
+        self._run("pcs_pure_vle_fast", params, temperature)
+
+    def run_retry(self, params, temperature):
+        self._run("pcs_pure_vle_retry", params, temperature)
+
+    def retry_count(self):
+        """Rows of the last run that left the main kernel: (all-fp64 fallback rows, robust-pass rows)."""
+        cnt = int(self.ws[0].item())
+        entries = self.ws[1:1 + cnt]
+        fallback = int((entries < 0).sum().item())  # bit 31 set
+        return fallback, cnt - fallback
+
+
+# ------------------------------------------------------------------------------------------
+# binary mixtures
+# ------------------------------------------------------------------------------------------
+def mix_bubble_dew(params, kij, temperature, molefracs, pressure, dew, want_iters=False):
+    """Bubble (dew=False) / dew (dew=True) points.  -> dict(p [Pa], rho4 [n,4] A^-3 = (rhoV_1, rhoV_2,
+    rhoL_1, rhoL_2), status bool, iters)."""
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    molefracs = _prep(molefracs, device)
+    pressure = _prep(pressure, device)
+    n = temperature.shape[0]
+    if not (params.shape[0] == kij.shape[0] == molefracs.shape[0] == pressure.shape[0] == n):
+        raise ValueError("inputs differ in length")
+    p, rho4 = _news(device, n, (n, 4))
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
+    ws = _workspace(n, device, mix=True)
+    _call(device, "pcs_mix_bubble_dew", int(bool(dew)), params, kij, temperature, molefracs, pressure, n, p, rho4, status,
+          iters, ws)
+    return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
+
+
+def mix_derivatives(params, kij, temperature, density):
+    """(a [n], p [n], mu [n,2], v [n,2]) — PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420)."""
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    density = _prep(density, device, (2,))
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij, density=density)
+    a, p, mu, v = _news(device, n, n, (n, 2), (n, 2))
+    _call(device, "pcs_mix_derivatives", params, kij, temperature, density, n, a, p, mu, v)
+    return a, p, mu, v
+
+
+def mix_stability(params, kij, temperature, density):
+    """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
+    density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,
+    3 invalid feed)."""
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    density = _prep(density, device, (2,))
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij, density=density)
+    tpd, rho_trial = _news(device, n, (n, 2))
+    status = _new(device, n, dtype=torch.uint8)
+    _call(device, "pcs_mix_stability", params, kij, temperature, density, n, tpd, rho_trial, status)
+    return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
+
+
+def _pcsaft_bubble_dew(parameters, kij, temperature, molefracs, pressure, dew):
+    parameters = _as_f64(parameters, 3)
+    kij = _as_f64(kij, 2)
+    temperature, molefracs, pressure = _as_f64(temperature, 1), _as_f64(molefracs, 1), _as_f64(pressure, 1)
+    r = mix_bubble_dew(torch.from_numpy(parameters), torch.from_numpy(kij), torch.from_numpy(temperature),
+                       torch.from_numpy(molefracs), torch.from_numpy(pressure), dew)
+    return Compaction(r["status"]).gather(r["rho4"]).cpu().numpy(), r["status"].cpu().numpy()  # filter_binary (:216-231)
 
 
 class PcSaft:
@@ -348,139 +459,15 @@ class PcSaft:
                                 torch.from_numpy(pressure))
         return Compaction(r["status"]).gather(r["rho_root"]).cpu().numpy(), r["status"].cpu().numpy()
 
+    @staticmethod
+    def bubble_point(parameters, kij, temperature, liquid_molefracs, pressure):
+        """src/pcsaft.rs:43-60 — rho[n_ok, 4] = (rhoV_1, rhoV_2, rhoL_1, rhoL_2), status[N]."""
+        return _pcsaft_bubble_dew(parameters, kij, temperature, liquid_molefracs, pressure, False)
 
-def _as_f64(x, ndim):
-    x = np.asarray(x)
-    if x.dtype != np.float64:
-        raise TypeError(f"argument must be a float64 array, got {x.dtype}")  # PyReadonlyArray<f64>
-    if x.ndim != ndim:
-        raise TypeError(f"argument must be {ndim}-dimensional, got {x.ndim}")
-    return np.ascontiguousarray(x)
-
-
-class PureVlePlan:
-    """Pre-allocated launch plan for repeated pure-VLE solves on a fixed number of rows: all
-    outputs and the retry workspace are allocated once; ``run`` only enqueues kernels on the
-    current HIP stream (no allocation, no host synchronisation), so steps can be timed with
-    HIP events."""
-
-    def __init__(self, n, device, want_rho_eq=False, want_rho_vl=False, all_fp64=False):
-        self.all_fp64 = bool(all_fp64)
-        self.n = int(n)
-        self.device = torch.device(device)
-        self._L = _lib.lib()
-        with torch.cuda.device(self.device):
-            self.p_sat = torch.empty(self.n, dtype=_F64, device=self.device)
-            self.rho_eq = torch.empty(self.n, dtype=_F64, device=self.device) if want_rho_eq else None
-            self.rho_vl = torch.empty((self.n, 2), dtype=_F64, device=self.device) if want_rho_vl else None
-            self.status = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            self.ws = torch.empty(max(1, self._L.pcs_workspace_bytes(self.n) // 4), dtype=torch.int32,
-                                  device=self.device)
-
-    def _args(self, params, temperature):
-        return (_lib.ptr(params), _lib.ptr(temperature), self.n, _lib.ptr(self.p_sat), _lib.ptr(self.rho_eq),
-                _lib.ptr(self.rho_vl), _lib.ptr(self.status), None, _lib.ptr(self.ws),
-                _lib.current_stream_ptr(self.device))
-
-    def run(self, params, temperature):
-        fn = self._L.pcs_pure_vle_fp64 if self.all_fp64 else self._L.pcs_pure_vle
-        _lib.check(fn(*self._args(params, temperature)), "pcs_pure_vle")
-
-    def run_fast(self, params, temperature):
-        _lib.check(self._L.pcs_pure_vle_fast(*self._args(params, temperature)), "pcs_pure_vle_fast")
-
-    def run_retry(self, params, temperature):
-        _lib.check(self._L.pcs_pure_vle_retry(*self._args(params, temperature)), "pcs_pure_vle_retry")
-
-    def retry_count(self):
-        """Rows of the last run that left the main kernel: (all-fp64 fallback rows, robust-pass rows)."""
-        cnt = int(self.ws[0].item())
-        entries = self.ws[1:1 + cnt]
-        fallback = int((entries < 0).sum().item())  # bit 31 set
-        return fallback, cnt - fallback
-
-
-# ------------------------------------------------------------------------------------------
-# binary mixtures
-# ------------------------------------------------------------------------------------------
-def mix_bubble_dew(params, kij, temperature, molefracs, pressure, dew, want_iters=False):
-    """Bubble (dew=False) / dew (dew=True) points.  -> dict(p [Pa], rho4 [n,4] A^-3 = (rhoV_1, rhoV_2,
-    rhoL_1, rhoL_2), status bool, iters)."""
-    device = _device_of(params)
-    params = _prep(params, device, (2, 8))
-    kij = _prep(kij, device, (2,))
-    temperature = _prep(temperature, device)
-    molefracs = _prep(molefracs, device)
-    pressure = _prep(pressure, device)
-    n = temperature.shape[0]
-    if not (params.shape[0] == kij.shape[0] == molefracs.shape[0] == pressure.shape[0] == n):
-        raise ValueError("inputs differ in length")
-    p = torch.empty(n, dtype=_F64, device=device)
-    rho4 = torch.empty((n, 4), dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
-    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
-    ws = _workspace(n, device, mix=True)
-    _call(device, "pcs_mix_bubble_dew", int(bool(dew)), params, kij, temperature, molefracs, pressure, n, p, rho4, status,
-          iters, ws)
-    return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
-
-
-def mix_derivatives(params, kij, temperature, density):
-    """(a [n], p [n], mu [n,2], v [n,2]) — PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420)."""
-    device = _device_of(params)
-    params = _prep(params, device, (2, 8))
-    kij = _prep(kij, device, (2,))
-    temperature = _prep(temperature, device)
-    density = _prep(density, device, (2,))
-    n = temperature.shape[0]
-    _same_rows(n, parameters=params, kij=kij, density=density)
-    a = torch.empty(n, dtype=_F64, device=device)
-    p = torch.empty(n, dtype=_F64, device=device)
-    mu = torch.empty((n, 2), dtype=_F64, device=device)
-    v = torch.empty((n, 2), dtype=_F64, device=device)
-    _call(device, "pcs_mix_derivatives", params, kij, temperature, density, n, a, p, mu, v)
-    return a, p, mu, v
-
-
-def mix_stability(params, kij, temperature, density):
-    """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
-    density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,
-    3 invalid feed)."""
-    device = _device_of(params)
-    params = _prep(params, device, (2, 8))
-    kij = _prep(kij, device, (2,))
-    temperature = _prep(temperature, device)
-    density = _prep(density, device, (2,))
-    n = temperature.shape[0]
-    _same_rows(n, parameters=params, kij=kij, density=density)
-    tpd = torch.empty(n, dtype=_F64, device=device)
-    rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
-    _call(device, "pcs_mix_stability", params, kij, temperature, density, n, tpd, rho_trial, status)
-    return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
-
-
-def _pcsaft_bubble_dew(parameters, kij, temperature, molefracs, pressure, dew):
-    parameters = _as_f64(parameters, 3)
-    kij = _as_f64(kij, 2)
-    temperature, molefracs, pressure = _as_f64(temperature, 1), _as_f64(molefracs, 1), _as_f64(pressure, 1)
-    r = mix_bubble_dew(torch.from_numpy(parameters), torch.from_numpy(kij), torch.from_numpy(temperature),
-                       torch.from_numpy(molefracs), torch.from_numpy(pressure), dew)
-    return Compaction(r["status"]).gather(r["rho4"]).cpu().numpy(), r["status"].cpu().numpy()  # filter_binary (:216-231)
-
-
-def _bubble_point(parameters, kij, temperature, liquid_molefracs, pressure):
-    """src/pcsaft.rs:43-60 — rho[n_ok, 4] = (rhoV_1, rhoV_2, rhoL_1, rhoL_2), status[N]."""
-    return _pcsaft_bubble_dew(parameters, kij, temperature, liquid_molefracs, pressure, False)
-
-
-def _dew_point(parameters, kij, temperature, vapor_molefracs, pressure):
-    """src/pcsaft.rs:62-79."""
-    return _pcsaft_bubble_dew(parameters, kij, temperature, vapor_molefracs, pressure, True)
-
-
-PcSaft.bubble_point = staticmethod(_bubble_point)
-PcSaft.dew_point = staticmethod(_dew_point)
+    @staticmethod
+    def dew_point(parameters, kij, temperature, vapor_molefracs, pressure):
+        """src/pcsaft.rs:62-79."""
+        return _pcsaft_bubble_dew(parameters, kij, temperature, vapor_molefracs, pressure, True)
 
 
 def mix_jacobian(params, kij, temperature, rho4, dew):
@@ -492,7 +479,7 @@ def mix_jacobian(params, kij, temperature, rho4, dew):
     rho4 = _prep(rho4, device, (4,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, rho4=rho4)
-    jac = torch.empty((n, 19), dtype=_F64, device=device)
+    jac = _new(device, (n, 19))
     ws = _workspace(n, device)
     _call(device, "pcs_mix_jacobian", int(bool(dew)), params, kij, temperature, rho4, n, jac, ws)
     return jac
@@ -556,10 +543,9 @@ def gc_bubble_dew(table, S, rows, phi, temperature, molefracs, pressure, dew, wa
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, molefracs=molefracs, pressure=pressure)
     _check_order(order, n, device)
-    p = torch.empty(n, dtype=_F64, device=device)
-    rho4 = torch.empty((n, 4), dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
-    iters = torch.empty(n, dtype=torch.int32, device=device) if want_iters else None
+    p, rho4 = _news(device, n, (n, 4))
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
     ws = _workspace(n, device)
     _call(device, "pcs_gc_bubble_dew", int(bool(dew)), table, int(S), rows, phi, temperature, molefracs, pressure, n, p,
           rho4, status, iters, order, ws)
@@ -574,10 +560,7 @@ def gc_derivatives(table, S, rows, phi, temperature, density):
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density)
-    a = torch.empty(n, dtype=_F64, device=device)
-    p = torch.empty(n, dtype=_F64, device=device)
-    mu = torch.empty((n, 2), dtype=_F64, device=device)
-    v = torch.empty((n, 2), dtype=_F64, device=device)
+    a, p, mu, v = _news(device, n, n, (n, 2), (n, 2))
     _call(device, "pcs_gc_derivatives", table, int(S), rows, phi, temperature, density, n, a, p, mu, v)
     return a, p, mu, v
 
@@ -593,9 +576,8 @@ def gc_stability(table, S, rows, phi, temperature, density, order=None):
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density)
     _check_order(order, n, device)
-    tpd = torch.empty(n, dtype=_F64, device=device)
-    rho_trial = torch.empty((n, 2), dtype=_F64, device=device)
-    status = torch.empty(n, dtype=torch.uint8, device=device)
+    tpd, rho_trial = _news(device, n, (n, 2))
+    status = _new(device, n, dtype=torch.uint8)
     _call(device, "pcs_gc_stability", table, int(S), rows, phi, temperature, density, n, tpd, rho_trial, status, order)
     return {"tpd": tpd, "rho_trial": rho_trial, "status": status}
 
@@ -609,10 +591,9 @@ def gc_jacobian(table, S, rows, phi, temperature, rho4, dew, order=None):
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, rho4=rho4)
-    jac = torch.empty((n, 7), dtype=_F64, device=device)
-    agg = torch.empty((n, 6), dtype=_F64, device=device)
+    jac, agg = _news(device, (n, 7), (n, 6))
     _call(device, "pcs_gc_jacobian", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, jac, agg,
-          order if order is not None and order.shape[0] == n else None)
+          _order_or_none(order, n))
     return jac, agg
 
 
@@ -628,7 +609,7 @@ def gc_segment_gradient(table, S, rows, phi, temperature, rho4, dew, gout=None, 
     _same_rows(n, phi=phi, rho4=rho4, gout=gout)
     grad = torch.zeros((int(S), 8), dtype=_F64, device=device)
     _call(device, "pcs_gc_segment_gradient", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, gout, grad,
-          order if order is not None and order.shape[0] == n else None)
+          _order_or_none(order, n))
     return grad
 
 
@@ -644,9 +625,7 @@ def pure_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_dp=
     g_a, g_p, g_dp = _opt(g_a, device), _opt(g_p, device), _opt(g_dp, device)
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density, g_a=g_a, g_p=g_p, g_dp=g_dp)
-    gpar = torch.empty((n, 8), dtype=_F64, device=device)
-    gT = torch.empty(n, dtype=_F64, device=device)
-    grho = torch.empty(n, dtype=_F64, device=device)
+    gpar, gT, grho = _news(device, (n, 8), n, n)
     _call(device, "pcs_pure_derivatives_vjp", params, temperature, density, n, g_a, g_p, g_dp, gpar, gT, grho)
     return gpar, gT, grho
 
@@ -660,7 +639,7 @@ def mix_derivatives_vjp(params, kij, temperature, density, g_a=None, g_p=None, g
     g_a, g_p, g_mu, g_v = _opt(g_a, device), _opt(g_p, device), _opt(g_mu, device, (2,)), _opt(g_v, device, (2,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, kij=kij, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    grad = torch.empty((n, 21), dtype=_F64, device=device)
+    grad = _new(device, (n, 21))
     ws = _workspace(n, device)
     _call(device, "pcs_mix_derivatives_vjp", params, kij, temperature, density, n, g_a, g_p, g_mu, g_v, grad, ws)
     return grad
@@ -676,10 +655,9 @@ def gc_derivatives_vjp(table, S, rows, phi, temperature, density, g_a=None, g_p=
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
     gseg = torch.zeros((int(S), 8), dtype=_F64, device=device)
-    jac9 = torch.empty((n, 9), dtype=_F64, device=device)
-    agg = torch.empty((n, 6), dtype=_F64, device=device)
+    jac9, agg = _news(device, (n, 9), (n, 6))
     _call(device, "pcs_gc_derivatives_vjp", table, int(S), rows, phi, temperature, density, n, g_a, g_p, g_mu, g_v, gseg,
-          jac9, agg, order if order is not None and order.shape[0] == n else None)
+          jac9, agg, _order_or_none(order, n))
     return gseg, jac9, agg
 
 
@@ -694,10 +672,7 @@ def mixn_derivatives(params, temperature, density):
     density = _prep(density, device, (nc,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density)
-    a = torch.empty(n, dtype=_F64, device=device)
-    p = torch.empty(n, dtype=_F64, device=device)
-    mu = torch.empty((n, nc), dtype=_F64, device=device)
-    v = torch.empty((n, nc), dtype=_F64, device=device)
+    a, p, mu, v = _news(device, n, n, (n, nc), (n, nc))
     _call(device, "pcs_mixn_derivatives", params, temperature, density, nc, n, a, p, mu, v)
     return a, p, mu, v
 
@@ -712,6 +687,6 @@ def mixn_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_mu=
     g_a, g_p, g_mu, g_v = _opt(g_a, device), _opt(g_p, device), _opt(g_mu, device, (nc,)), _opt(g_v, device, (nc,))
     n = temperature.shape[0]
     _same_rows(n, parameters=params, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    grad = torch.empty((n, 9 * nc + 1), dtype=_F64, device=device)
+    grad = _new(device, (n, 9 * nc + 1))
     _call(device, "pcs_mixn_derivatives_vjp", params, temperature, density, nc, n, g_a, g_p, g_mu, g_v, grad)
     return grad

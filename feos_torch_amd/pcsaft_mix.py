@@ -12,94 +12,66 @@ zero gradient there; here they receive none).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import native
+from . import _shell, native
+from .native import _detached
+
+
+_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, temperature in the [n,19] Jacobian
 
 
 class _BubbleDew(torch.autograd.Function):
-    """value[n_ok], nans[n] = bubble / dew pressure.  Dense solve, one compaction plan (its 4-byte row count is the call's only
-    host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the reference drops them
-    inside the native call, src/pcsaft.rs:216-231)."""
+    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew pressure.  Dense solve, one compaction plan (its 4-byte row
+    count is the call's only host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the
+    reference drops them inside the native call, src/pcsaft.rs:216-231)."""
 
     @staticmethod
-    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, box, check=False):
-        out_device = parameters.device
-        dev = native._dev() if not parameters.is_cuda else parameters.device
+    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, check=False):
+        dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (2, 8))
         k = native._prep(kij, dev, (2,))
         T = native._prep(temperature, dev)
-        z = native._prep(molefracs, dev)
-        p0 = native._prep(pressure, dev)
-        r = native.mix_bubble_dew(par, k, T, z, p0, dew)
-        nans = r["status"]
-        comp = native.Compaction(nans)
-        box.append(comp)
+        r = native.mix_bubble_dew(par, k, T, native._prep(molefracs, dev), native._prep(pressure, dev), dew)
+        comp = native.Compaction(r["status"])
         value = comp.gather(r["p"])
-        needs = list(ctx.needs_input_grad[1:4])
-        if any(needs):
+        ctx.needs = list(ctx.needs_input_grad[1:4])
+        if any(ctx.needs):
             jac = native.mix_jacobian(comp.gather(par), comp.gather(k), comp.gather(T), comp.gather(r["rho4"]), dew)
             ctx.save_for_backward(jac)
             ctx.comp = comp
-        ctx.needs = needs
         ctx.in_devices = (parameters.device, kij.device, temperature.device)
-        nans = nans.to(out_device)
+        flags = ()
         if check:
-            # stability of the specified phase at the converged solution (liquid for bubble, vapour for dew), on the
-            # compacted rows: aligned with `value`
-            rho4 = comp.gather(r["rho4"])
-            feed = rho4[:, 0:2] if dew else rho4[:, 2:4]
-            st = native.mix_stability(comp.gather(par), comp.gather(k), comp.gather(T), feed)["status"]
-            stable = (st == 0).to(out_device)
-            ctx.mark_non_differentiable(nans, stable)
-            return value.to(out_device), nans, stable
-        ctx.mark_non_differentiable(nans)
-        return value.to(out_device), nans
+            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
+                comp.gather(par), comp.gather(k), comp.gather(T), feed)),)
+        return (*_shell.finish(ctx, parameters.device, [value], r["status"], *flags), comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, _g_nans, *_g_stable):
+    def backward(ctx, g_value, *_g_flags):
         (jac,) = ctx.saved_tensors
-        comp = ctx.comp
-        g = g_value.to(jac.device).contiguous()
-        n = comp.n
-        gp = gk = gt = None
-        if ctx.needs[0]:
-            gp = comp.expand(jac, g, 0, 16).view(n, 2, 8).to(ctx.in_devices[0])
-        if ctx.needs[1]:
-            gk = comp.expand(jac, g, 16, 2).to(ctx.in_devices[1])
-        if ctx.needs[2]:
-            gt = comp.expand(jac, g, 18, 1).view(n).to(ctx.in_devices[2])
-        return None, gp, gk, gt, None, None, None, None
+        return (None, *_shell.scatter(ctx.comp, jac, g_value, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None)
 
 
 class _MixDerivatives(torch.autograd.Function):
     """(a, p, mu, v) = derivatives(parameters[n,2,8], kij[n,2], temperature[n], density[n,2]) with gradients to all four
     inputs (feos_torch/pcsaft_mix.py:31-154, :395-420 are torch graphs in the reference)."""
 
+    COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)), (19, 2, (-1, 2)))  # of the packed gradient [n,21]
+
     @staticmethod
     def forward(ctx, parameters, kij, temperature, density):
-        dev = native._dev() if not parameters.is_cuda else parameters.device
-        par = native._prep(parameters, dev, (2, 8))
-        k = native._prep(kij, dev, (2,))
-        T = native._prep(temperature, dev)
-        rho = native._prep(density, dev, (2,))
-        a, p, mu, v = native.mix_derivatives(par, k, T, rho)
-        ctx.save_for_backward(par, k, T, rho)
-        ctx.set_materialize_grads(False)
-        ctx.in_devices = (parameters.device, kij.device, temperature.device, density.device)
-        out = parameters.device
-        return a.to(out), p.to(out), mu.to(out), v.to(out)
+        dev = native._device_of(parameters)
+        saved = (native._prep(parameters, dev, (2, 8)), native._prep(kij, dev, (2,)), native._prep(temperature, dev),
+                 native._prep(density, dev, (2,)))
+        return _shell.save_state(ctx, (parameters, kij, temperature, density), saved, native.mix_derivatives(*saved))
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_a, g_p, g_mu, g_v):
-        par, k, T, rho = ctx.saved_tensors
-        if g_a is None and g_p is None and g_mu is None and g_v is None:
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
             return None, None, None, None
-        g = native.mix_derivatives_vjp(par, k, T, rho, g_a, g_p, g_mu, g_v)
-        need, d = ctx.needs_input_grad, ctx.in_devices
-        n = T.shape[0]
-        return (g[:, 0:16].reshape(n, 2, 8).to(d[0]) if need[0] else None, g[:, 16:18].contiguous().to(d[1]) if need[1] else None,
-                g[:, 18].contiguous().to(d[2]) if need[2] else None, g[:, 19:21].contiguous().to(d[3]) if need[3] else None)
+        g = native.mix_derivatives_vjp(*ctx.saved_tensors, *grads)
+        return _shell.split(g, _MixDerivatives.COLUMNS, ctx.needs_input_grad, ctx.in_devices)
 
 
 class _MixnDerivatives(torch.autograd.Function):
@@ -108,32 +80,23 @@ class _MixnDerivatives(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, parameters, temperature, density):
-        dev = native._dev() if not parameters.is_cuda else parameters.device
+        dev = native._device_of(parameters)
         nc = int(parameters.shape[1])
-        par = native._prep(parameters, dev, (nc, 8))
-        T = native._prep(temperature, dev)
-        rho = native._prep(density, dev, (nc,))
-        a, p, mu, v = native.mixn_derivatives(par, T, rho)
-        ctx.save_for_backward(par, T, rho)
-        ctx.set_materialize_grads(False)
-        ctx.in_devices = (parameters.device, temperature.device, density.device)
-        out = parameters.device
-        return a.to(out), p.to(out), mu.to(out), v.to(out)
+        saved = (native._prep(parameters, dev, (nc, 8)), native._prep(temperature, dev), native._prep(density, dev, (nc,)))
+        return _shell.save_state(ctx, (parameters, temperature, density), saved, native.mixn_derivatives(*saved))
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_a, g_p, g_mu, g_v):
-        par, T, rho = ctx.saved_tensors
-        if g_a is None and g_p is None and g_mu is None and g_v is None:
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
             return None, None, None
-        n, nc = rho.shape
-        g = native.mixn_derivatives_vjp(par, T, rho, g_a, g_p, g_mu, g_v)
-        need, d = ctx.needs_input_grad, ctx.in_devices
-        return (g[:, : 8 * nc].reshape(n, nc, 8).to(d[0]) if need[0] else None, g[:, 8 * nc].contiguous().to(d[1]) if need[1] else None,
-                g[:, 8 * nc + 1:].contiguous().to(d[2]) if need[2] else None)
+        nc = ctx.saved_tensors[2].shape[1]
+        g = native.mixn_derivatives_vjp(*ctx.saved_tensors, *grads)  # [n, 9 nc + 1]
+        columns = ((0, 8 * nc, (-1, nc, 8)), (8 * nc, 1, (-1,)), (8 * nc + 1, nc, (-1, nc)))
+        return _shell.split(g, columns, ctx.needs_input_grad, ctx.in_devices)
 
 
-class PcSaftMix:
+class PcSaftMix(_shell.Reducible):
     def __init__(self, parameters, kij=None):
         """parameters: [N, 2, 8] float64 (component rows as for PcSaftPure); kij: [N, 2] with
         kij[:,0] = k_ij and kij[:,1] = explicit cross-association energy eps_AiBj/k or 0
@@ -196,12 +159,11 @@ class PcSaftMix:
     def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
         if self.ncomp != 2:
             raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
-        box = []
         # mole fractions and initial pressure do not enter the reference's final formula (:435-444): no gradient flows to them
-        out = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure), box,
-                               bool(check_stability))
-        self._reduce(box[0])
-        return out
+        *out, comp = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure),
+                                      bool(check_stability))
+        self._reduce(comp)
+        return tuple(out)
 
     def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
         """(p [Pa], nans) at T [K], liquid mole fraction of component 1, initial pressure [Pa] (:422-444).
@@ -229,15 +191,6 @@ class PcSaftMix:
             out = self._par.device
             return (r["status"] == 0).to(out), r["tpd"].to(out), r["rho_trial"].to(out)
 
-    def _reduce(self, comp):
+    def _reduce(self, comp):  # `reduce(nans)` (:470-479) is _shell.Reducible's
         if not comp.all_ok:
             self._set(native.compact_rows(comp, self._par), None if self.kij is None else native.compact_rows(comp, self.kij))
-
-    def reduce(self, nans):
-        """Drop the rows flagged in ``nans`` (:470-479)."""
-        dev = self._par.device if self._par.is_cuda else native._dev()
-        self._reduce(native.Compaction(nans.to(dev)))
-
-
-def _detached(x):
-    return x.detach() if isinstance(x, torch.Tensor) else x

@@ -16,11 +16,14 @@ back on the device of ``parameters``.
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import native
+from . import _shell, native
+
+
+_COLUMNS = ((0, 8, (-1, 8)), (8, 1, (-1,)), (9, 1, (-1,)))  # parameters, temperature, pressure in the [n,10] Jacobian
 
 
 class _PureProperty(torch.autograd.Function):
-    """value[n_ok], nans[n] = property(parameters[n,8], temperature[n], pressure[n] or None)
+    """value[n_ok], nans[n], plan = property(parameters[n,8], temperature[n], pressure[n] or None)
 
     One solve (dense outputs + status byte per row), one compaction plan whose 4-byte row count is the call's only host
     synchronisation, then -- only if rows were dropped -- single-kernel gathers (native.Compaction; the reference drops
@@ -28,28 +31,23 @@ class _PureProperty(torch.autograd.Function):
     requested: the vapour pressure always comes from the pressure-only kernel (pcs_pure_vapor_pressure)."""
 
     @staticmethod
-    def forward(ctx, which, parameters, temperature, pressure, box):
-        out_device = parameters.device
-        dev = native._dev() if not parameters.is_cuda else parameters.device
+    def forward(ctx, which, parameters, temperature, pressure):
+        dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (8,))
         T = native._prep(temperature, dev)
+        P = None
         needs = list(ctx.needs_input_grad[1:4])
         if which == "liquid_density":
             P = native._prep(pressure, dev)
             r = native.pure_liquid_density(par, T, P)
             value = r["rho"]
-            rho_vl = None
         elif which == "vapor_pressure":
-            P = None
             r = native.pure_vapor_pressure(par, T, want_rho_vl=any(needs))
-            value, rho_vl = r["p_sat"], r["rho_vl"]
+            value = r["p_sat"]
         else:
-            P = None
             r = native.pure_vle(par, T, want_p=False, want_rho_eq=True, want_rho_vl=any(needs))
-            value, rho_vl = r["rho_eq"], r["rho_vl"]
-        nans = r["status"]
-        comp = native.Compaction(nans)
-        box.append(comp)  # handed to the model for its `reduce`
+            value = r["rho_eq"]
+        comp = native.Compaction(r["status"])
         value = comp.gather(value)
         if any(needs):
             # Jacobian only on converged rows (dense kernel on the compacted inputs)
@@ -57,7 +55,7 @@ class _PureProperty(torch.autograd.Function):
                 root = comp.gather(r["rho_root"])
                 rho_vl = torch.stack([torch.zeros_like(root), root], dim=1)
             else:
-                rho_vl = comp.gather(rho_vl)
+                rho_vl = comp.gather(r["rho_vl"])
             if comp.all_ok:
                 # every row converged (the common case): the Jacobian kernel runs in backward, in vector-Jacobian form, and
                 # writes g * d value / d (parameters, T, p) straight into the gradient arrays
@@ -70,32 +68,19 @@ class _PureProperty(torch.autograd.Function):
             ctx.which = which
         ctx.needs = needs
         ctx.in_devices = (parameters.device, temperature.device, None if pressure is None else pressure.device)
-        nans = nans.to(out_device)
-        ctx.mark_non_differentiable(nans)
-        return value.to(out_device), nans
+        return (*_shell.finish(ctx, parameters.device, [value], r["status"]), comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, _g_nans):
+    def backward(ctx, g_value, _g_nans, _g_plan):
         comp = ctx.comp
-        g = g_value.to(comp.device).contiguous()
-        gp = gt = gpr = None
         if comp.all_ok:
             par, T, rho_vl, *rest = ctx.saved_tensors
-            gp, gt, gpr = native.pure_jacobian_vjp(ctx.which, par, T, rest[0] if rest else None, rho_vl, g, ctx.needs,
-                                                   polish=(ctx.which == "vapor_pressure"))
-            dv = ctx.in_devices
-            return (None, None if gp is None else gp.to(dv[0]), None if gt is None else gt.to(dv[1]),
-                    None if gpr is None else gpr.to(dv[2]), None)
+            grads = native.pure_jacobian_vjp(ctx.which, par, T, rest[0] if rest else None, rho_vl,
+                                             g_value.to(comp.device).contiguous(), ctx.needs, polish=(ctx.which == "vapor_pressure"))
+            return (None, *(None if g is None else g.to(dev) for g, dev in zip(grads, ctx.in_devices)))
         (jac,) = ctx.saved_tensors
-        # dense gradient rows in one kernel each: g_j * jac[j, cols] scattered to the row's place, zeros for dropped rows
-        if ctx.needs[0]:
-            gp = comp.expand(jac, g, 0, 8).to(ctx.in_devices[0])
-        if ctx.needs[1]:
-            gt = comp.expand(jac, g, 8, 1).view(comp.n).to(ctx.in_devices[1])
-        if ctx.needs[2]:
-            gpr = comp.expand(jac, g, 9, 1).view(comp.n).to(ctx.in_devices[2])
-        return None, gp, gt, gpr, None
+        return (None, *_shell.scatter(comp, jac, g_value, _COLUMNS, ctx.needs, ctx.in_devices))
 
 
 class _PureDerivatives(torch.autograd.Function):
@@ -104,72 +89,57 @@ class _PureDerivatives(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, parameters, temperature, density):
-        dev = native._dev() if not parameters.is_cuda else parameters.device
-        par = native._prep(parameters, dev, (8,))
-        T = native._prep(temperature, dev)
-        rho = native._prep(density, dev)
-        a, p, dp = native.pure_derivatives(par, T, rho)
-        ctx.save_for_backward(par, T, rho)
-        ctx.set_materialize_grads(False)
-        ctx.in_devices = (parameters.device, temperature.device, density.device)
-        out = parameters.device
-        return a.to(out), p.to(out), dp.to(out)
+        dev = native._device_of(parameters)
+        saved = (native._prep(parameters, dev, (8,)), native._prep(temperature, dev), native._prep(density, dev))
+        return _shell.save_state(ctx, (parameters, temperature, density), saved, native.pure_derivatives(*saved))
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_a, g_p, g_dp):
-        par, T, rho = ctx.saved_tensors
-        if g_a is None and g_p is None and g_dp is None:
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
             return None, None, None
-        gpar, gT, grho = native.pure_derivatives_vjp(par, T, rho, g_a, g_p, g_dp)
-        need = ctx.needs_input_grad
-        return (gpar.to(ctx.in_devices[0]) if need[0] else None, gT.to(ctx.in_devices[1]) if need[1] else None,
-                grho.to(ctx.in_devices[2]) if need[2] else None)
+        pieces = native.pure_derivatives_vjp(*ctx.saved_tensors, *grads)
+        return tuple(g.to(dev) if need else None for g, dev, need in zip(pieces, ctx.in_devices, ctx.needs_input_grad))
 
 
 class _PureCritical(torch.autograd.Function):
-    """t_c[n_ok], p_c[n_ok], rho_c[n_ok], nans[n] = critical_point(parameters[n,8], initial temperature[n] or None)
+    """t_c[n_ok], p_c[n_ok], rho_c[n_ok], nans[n], plan = critical_point(parameters[n,8], initial temperature[n] or None)
 
     One solve, one compaction plan (its 4-byte count is the call's only host synchronisation); the backward pass is the
     implicit-function kernel on the converged rows (pcs_pure_critical_point_vjp), dropped rows receive zero gradient."""
 
     @staticmethod
-    def forward(ctx, parameters, initial_temperature, box):
-        out_device = parameters.device
-        dev = native._dev() if not parameters.is_cuda else parameters.device
+    def forward(ctx, parameters, initial_temperature):
+        dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (8,))
         t0 = None if initial_temperature is None else native._prep(initial_temperature, dev)
         r = native.pure_critical_point(par, t0)
-        nans = r["status"]
-        comp = native.Compaction(nans)
-        box.append(comp)
+        comp = native.Compaction(r["status"])
         tc, pc, rhoc = comp.gather(r["t_c"]), comp.gather(r["p_c"]), comp.gather(r["rho_c"])
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(comp.gather(par), tc, rhoc)
             ctx.comp = comp
         ctx.set_materialize_grads(False)
         ctx.in_device = parameters.device
-        nans = nans.to(out_device)
-        ctx.mark_non_differentiable(nans)
-        return tc.to(out_device), pc.to(out_device), rhoc.to(out_device), nans
+        return (*_shell.finish(ctx, parameters.device, [tc, pc, rhoc], r["status"]), comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_tc, g_pc, g_rhoc, _g_nans):
+    def backward(ctx, g_tc, g_pc, g_rhoc, _g_nans, _g_plan):
         if g_tc is None and g_pc is None and g_rhoc is None:
-            return None, None, None
+            return None, None
         par, tc, rhoc = ctx.saved_tensors
         comp = ctx.comp
         if comp.n_ok == 0:
-            return torch.zeros((comp.n, 8), dtype=torch.float64, device=ctx.in_device), None, None
+            return torch.zeros((comp.n, 8), dtype=torch.float64, device=ctx.in_device), None
         on = lambda g: None if g is None else g.to(comp.device).contiguous()
         gp = native.pure_critical_point_vjp(par, tc, rhoc, on(g_tc), on(g_pc), on(g_rhoc))
         if not comp.all_ok:
             gp = comp.expand(gp)
-        return gp.to(ctx.in_device), None, None
+        return gp.to(ctx.in_device), None
 
 
-class PcSaftPure:
+class PcSaftPure(_shell.Reducible):
     def __init__(self, parameters):
         """parameters: [N, 8] float64 — m, sigma, epsilon_k, mu, kappa_ab, epsilon_k_ab, na, nb
         (feos_torch/pcsaft_pure.py:90-104, README.md:12)."""
@@ -212,9 +182,8 @@ class PcSaftPure:
 
     # -- properties ------------------------------------------------------------------------
     def _property(self, which, temperature, pressure):
-        box = []
-        value, nans = _PureProperty.apply(which, self._par, temperature, pressure, box)
-        self._reduce(box[0])
+        value, nans, comp = _PureProperty.apply(which, self._par, temperature, pressure)
+        self._reduce(comp)
         return nans, value
 
     def liquid_density(self, temperature, pressure):
@@ -236,16 +205,10 @@ class PcSaftPure:
         initial_temperature [N] (optional): where the search for T_c starts.  Not part of the reference's class."""
         if initial_temperature is not None:
             initial_temperature = torch.as_tensor(initial_temperature, dtype=torch.float64)
-        box = []
-        t_c, p_c, rho_c, nans = _PureCritical.apply(self._par, initial_temperature, box)
-        self._reduce(box[0])
+        t_c, p_c, rho_c, nans, comp = _PureCritical.apply(self._par, initial_temperature)
+        self._reduce(comp)
         return nans, t_c, p_c, rho_c
 
-    def _reduce(self, comp):
+    def _reduce(self, comp):  # `reduce(nans)` (:235-243) is _shell.Reducible's
         if not comp.all_ok:
             self._par = native.compact_rows(comp, self._par)
-
-    def reduce(self, nans):
-        """Drop the rows flagged in ``nans`` from the model (:235-243)."""
-        dev = self._par.device if self._par.is_cuda else native._dev()
-        self._reduce(native.Compaction(nans.to(dev)))
