@@ -13,7 +13,9 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_C
            ("gc_kernels.hip", "gc_kernels.o", []), ("gc_gradient.hip", "gc_gradient.o", []),
            ("stability_kernels.hip", "stability_kernels.o", []),
            # critical points: strict IEEE semantics like pure_robust.hip (neither RELAXED nor REASSOC), csrc/pure_critical.hpp
-           ("pure_critical.hip", "pure_critical.o", [])]
+           ("pure_critical.hip", "pure_critical.o", []),
+           # boiling temperatures: strict IEEE as well (bracketing and failure detection), no fp32 pre-solve, csrc/pure_boiling.hpp
+           ("pure_boiling.hip", "pure_boiling.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,

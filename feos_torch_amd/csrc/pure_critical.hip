@@ -11,32 +11,15 @@
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
 #include "pure_critical.hpp"
+#include "pure_stage.hpp"
 
 using namespace pcs;
 using namespace pcs_abi;
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int ROW_PAD = 9;
-
-// rows past n are clamped to row n-1 (their results are never stored)
-__device__ __forceinline__ void stage_rows(const double* __restrict__ params, int64_t n, int64_t row0, double* lds) {
-    const int t = threadIdx.x;
-    const double2* src = reinterpret_cast<const double2*>(params);
-    const int64_t last2 = n * 4 - 1;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx2 = t + k * BLOCK;
-        int64_t g = row0 * 4 + idx2;
-        if (g > last2) g = last2 - 3 + (idx2 & 3);
-        const double2 v = src[g];
-        const int r = idx2 >> 2, c2 = idx2 & 3;
-        lds[r * ROW_PAD + 2 * c2] = v.x;
-        lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
-    }
-    __syncthreads();
-}
+constexpr int BLOCK = STAGE_BLOCK;  // stage_rows: pure_stage.hpp
+constexpr int ROW_PAD = STAGE_ROW_PAD;
 
 __global__ __launch_bounds__(BLOCK) void k_pure_critical(const double* __restrict__ params, const double* __restrict__ t_init,
                                                          int64_t n, double* __restrict__ tc, double* __restrict__ pc,

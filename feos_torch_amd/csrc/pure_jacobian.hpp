@@ -130,11 +130,28 @@ PCS_DEV void adjoint_axpy(const PureCoef<double>& c, PureCoefAdj<double>& adj, c
     if (c.assoc) { adj.da += w * pick(g.da); adj.na += w * pick(g.na); adj.nb += w * pick(g.nb); }
 }
 
-// WHICH: 0 vapor_pressure [Pa], 1 liquid_density [kmol/m3], 2 equilibrium_liquid_density [kmol/m3]
+// WHICH: 0 vapor_pressure [Pa], 1 liquid_density [kmol/m3], 2 equilibrium_liquid_density [kmol/m3],
+// 3 boiling_temperature [K]: T(parameters, p) with p_sat(parameters, T) = p, at the converged T and densities.  By the
+// implicit-function theorem on the vapour-pressure Jacobian g0 at that state:  dT/dtheta_k = -g0[k] / g0[8],
+// dT/dp = 1 / g0[8]  (g0[8] = dp_sat/dT, the Clapeyron slope); T is an output here, so its own column is 0.
 template <int WHICH>
 PCS_DEV void pure_jacobian(const double par[8], double T, double p_pa, double rv, double rl, double g[JAC_DIRS], bool polish = false) {
     typedef DN<double, JAC_CHUNK> G;
     constexpr int NPASS = (JAC_DIRS + JAC_CHUNK - 1) / JAC_CHUNK;
+    if constexpr (WHICH == 3) {
+        double g0[JAC_DIRS];
+        pure_jacobian<0>(par, T, 0.0, rv, rl, g0, false);
+        const double inv = 1.0 / g0[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) g[k] = -g0[k] * inv;
+        g[8] = 0.0;
+        g[9] = inv;
+        // the quotients are the Jacobian: pinned in registers, so that re-association cannot fold the cotangent of the
+        // vector-Jacobian form into `inv` (the vjp must equal gout x the Jacobian bit for bit)
+#pragma unroll
+        for (int k = 0; k < JAC_DIRS; k++) asm volatile("" : "+v"(g[k]));
+        return;
+    }
     {
         // Every property is  val = F(a_c(rho_V), a_c(rho_L), a'_c(rho_L); T, p)  with the densities fixed, so its parameter
         // derivative is  sum_k abar_k dc_k/dtheta + explicit T / p terms  with the coefficient adjoints abar from closed-form

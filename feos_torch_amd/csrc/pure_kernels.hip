@@ -350,7 +350,7 @@ __global__ __launch_bounds__(BLOCK, K4_WAVES) void k_pure_jacobian(const double*
     double par[8];
     // class bucketing as in k_pure_vle for the two liquid-density properties (A/B on 1e7 rows: 4.0 -> 3.9 ms and
     // 12.0 -> 8.4 ms; the vapour-pressure Jacobian gets slightly slower with it, 3.5 -> 3.7 ms, and keeps the row order)
-    constexpr bool BUCKET = WHICH != 0;
+    constexpr bool BUCKET = WHICH == 1 || WHICH == 2;  // the boiling-temperature Jacobian (3) is the vapour-pressure one at heart
     __shared__ int perm[BUCKET ? BLOCK : 1];
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(BLOCK, K4_WAVES) void k_pure_jacobian(const double*
 #pragma unroll
             for (int k = 0; k < 4; k++) dst[k] = make_double2(w * g[2 * k], w * g[2 * k + 1]);
         }
-        if (grad_temp) grad_temp[i] = w * g[8];
+        if (grad_temp) grad_temp[i] = (WHICH == 3) ? 0.0 : w * g[8];  // 3: T is the output, not an input
         if (grad_press) grad_press[i] = w * g[9];
     }
 }
@@ -443,9 +443,9 @@ int launch_pure_liquid_density(const double* params, const double* temp, const d
 #if PCS_PURE_PART == 1
 extern "C" {
 
-int pcs_abi_version(void) { return 107; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+int pcs_abi_version(void) { return 108; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
                                             // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp);
-                                            // 107: pcs_pure_start_probe
+                                            // 107: pcs_pure_start_probe; 108: pcs_pure_boiling_temperature, Jacobian selector 3
 
 const char* pcs_last_error(void) { return g_err; }
 
@@ -572,7 +572,8 @@ static int launch_pure_jacobian(const char* entry, int which, const double* para
         case 0: hipLaunchKernelGGL(k_pure_jacobian<0>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
         case 1: hipLaunchKernelGGL(k_pure_jacobian<1>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
         case 2: hipLaunchKernelGGL(k_pure_jacobian<2>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
-        default: return fail_msg(entry, "which must be 0, 1 or 2");
+        case 3: hipLaunchKernelGGL(k_pure_jacobian<3>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;
+        default: return fail_msg(entry, "which must be 0, 1, 2 or 3");
     }
     return launched("k_pure_jacobian launch");
 }

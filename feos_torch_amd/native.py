@@ -253,7 +253,7 @@ def pure_derivatives(params, temperature, density):
     return a, p, dp
 
 
-_WHICH = {"vapor_pressure": 0, "liquid_density": 1, "equilibrium_liquid_density": 2}
+_WHICH = {"vapor_pressure": 0, "liquid_density": 1, "equilibrium_liquid_density": 2, "boiling_temperature": 3}
 
 
 JAC_POLISH = 0x100  # PCS_JAC_POLISH (include/pcsaft_hip.h)
@@ -261,7 +261,8 @@ JAC_POLISH = 0x100  # PCS_JAC_POLISH (include/pcsaft_hip.h)
 
 def pure_jacobian(which, params, temperature, pressure, rho_vl, polish=False):
     """[n,10] Jacobian w.r.t. (8 parameters, T, p) at fixed densities.  polish: rho_vl are the pressure-only kernel's
-    densities (pure_vapor_pressure) and take one fp64 Newton step first."""
+    densities (pure_vapor_pressure) and take one fp64 Newton step first.  "boiling_temperature": temperature and rho_vl
+    are the outputs of pure_boiling_temperature, pressure may be None; column 8 is zero (T is the property)."""
     device = rho_vl.device
     params = _prep(params, device, (8,))
     temperature = _prep(temperature, device)
@@ -288,10 +289,27 @@ def pure_jacobian_vjp(which, params, temperature, pressure, rho_vl, gout, need=(
     _same_rows(n, parameters=params, pressure=pressure, rho_vl=rho_vl, gout=gout)
     gp = _new(device, (n, 8)) if need[0] else None
     gt = _new(device, n) if need[1] else None
-    gpr = _new(device, n) if (need[2] and pressure is not None) else None
+    gpr = _new(device, n) if (need[2] and (pressure is not None or which == "boiling_temperature")) else None
     _call(device, "pcs_pure_jacobian_vjp", _WHICH[which] | (JAC_POLISH if polish else 0), params, temperature, pressure,
           rho_vl, gout, n, gp, gt, gpr)
     return gp, gt, gpr
+
+
+def pure_boiling_temperature(parameters, pressure, initial_temperature=None, want_rho_vl=True, want_iters=False):
+    """Boiling temperature of every parameter row at `pressure` [Pa] (pcs_pure_boiling_temperature).
+    -> dict(t [K], rho_vl [n,2] A^-3 at t or None, status bool (True = failed), iters int32 or None)."""
+    device = _device_of(parameters)
+    parameters = _prep(parameters, device, (8,))
+    pressure = _prep(pressure, device)
+    t_init = None if initial_temperature is None else _prep(initial_temperature, device)
+    n = parameters.shape[0]
+    _same_rows(n, pressure=pressure, initial_temperature=t_init)
+    t = _new(device, n)
+    rho_vl = _new(device, (n, 2)) if want_rho_vl else None
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
+    _call(device, "pcs_pure_boiling_temperature", parameters, pressure, t_init, n, t, rho_vl, status, iters)
+    return {"t": t, "rho_vl": rho_vl, "status": status.view(torch.bool), "iters": iters}
 
 
 def pure_critical_point(params, initial_temperature=None, want_iters=False):

@@ -24,6 +24,7 @@ _COLUMNS = ((0, 8, (-1, 8)), (8, 1, (-1,)), (9, 1, (-1,)))  # parameters, temper
 
 class _PureProperty(torch.autograd.Function):
     """value[n_ok], nans[n], plan = property(parameters[n,8], temperature[n], pressure[n] or None)
+    ("boiling_temperature": the temperature argument is the optional first iterate and receives no gradient; the value is T)
 
     One solve (dense outputs + status byte per row), one compaction plan whose 4-byte row count is the call's only host
     synchronisation, then -- only if rows were dropped -- single-kernel gathers (native.Compaction; the reference drops
@@ -34,10 +35,15 @@ class _PureProperty(torch.autograd.Function):
     def forward(ctx, which, parameters, temperature, pressure):
         dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (8,))
-        T = native._prep(temperature, dev)
+        T = None if temperature is None else native._prep(temperature, dev)
         P = None
         needs = list(ctx.needs_input_grad[1:4])
-        if which == "liquid_density":
+        if which == "boiling_temperature":
+            needs[1] = False
+            P = native._prep(pressure, dev)
+            r = native.pure_boiling_temperature(par, P, T, want_rho_vl=any(needs))
+            value = T = r["t"]  # the Jacobian is taken at the solved temperature
+        elif which == "liquid_density":
             P = native._prep(pressure, dev)
             r = native.pure_liquid_density(par, T, P)
             value = r["rho"]
@@ -67,7 +73,7 @@ class _PureProperty(torch.autograd.Function):
             ctx.comp = comp
             ctx.which = which
         ctx.needs = needs
-        ctx.in_devices = (parameters.device, temperature.device, None if pressure is None else pressure.device)
+        ctx.in_devices = tuple(None if x is None else x.device for x in (parameters, temperature, pressure))
         return (*_shell.finish(ctx, parameters.device, [value], r["status"]), comp)
 
     @staticmethod
@@ -208,6 +214,19 @@ class PcSaftPure(_shell.Reducible):
         t_c, p_c, rho_c, nans, comp = _PureCritical.apply(self._par, initial_temperature)
         self._reduce(comp)
         return nans, t_c, p_c, rho_c
+
+    def boiling_temperature(self, pressure, initial_temperature=None):
+        """(nans, T [K]): the temperature at which every row boils at `pressure` [Pa], i.e. p_sat(T) = pressure -- the inverse
+        of `vapor_pressure`, solved in one kernel (csrc/pure_boiling.hpp).  Values for the converged rows only; a row fails when
+        its pressure is not below its critical pressure (or on the last 0.05 % of the saturation line below it, where part of
+        the rows fail), non-positive or non-finite.  Differentiable w.r.t. the parameters and the pressure (implicit-function
+        theorem on the vapour-pressure Jacobian: dT/dp = 1 / (dp_sat/dT)).
+        initial_temperature [N] (optional): first iterate of the search; it receives no gradient.
+        Not part of the reference's class."""
+        pressure = torch.as_tensor(pressure, dtype=torch.float64)
+        if initial_temperature is not None:
+            initial_temperature = torch.as_tensor(initial_temperature, dtype=torch.float64)
+        return self._property("boiling_temperature", initial_temperature, pressure)
 
     def _reduce(self, comp):  # `reduce(nans)` (:235-243) is _shell.Reducible's
         if not comp.all_ok:

@@ -121,7 +121,10 @@ int pcs_pure_start_probe(const double* params, const double* temp, int64_t n, fl
  * fixed — what torch reverse mode through the reference's Python tail yields
  * (feos_torch/pcsaft_pure.py:196-199 / :212-215 / :228-233).
  *   which    0 = vapor_pressure, 1 = liquid_density, 2 = equilibrium_liquid_density; 0 | PCS_JAC_POLISH: rho_vl comes
- *            from pcs_pure_vapor_pressure (~1e-9 from the root) and takes one fp64 Newton step before the derivatives
+ *            from pcs_pure_vapor_pressure (~1e-9 from the root) and takes one fp64 Newton step before the derivatives;
+ *            3 = boiling_temperature: temp [n] and rho_vl [n,2] are the outputs of pcs_pure_boiling_temperature (converged:
+ *            no PCS_JAC_POLISH), pressure may be NULL.  With g0 the which = 0 Jacobian at that state (implicit-function
+ *            theorem on p_sat(parameters, T) = p):  jac[k] = -g0[k] / g0[8] (k < 8),  jac[8] = 0,  jac[9] = 1 / g0[8]
  *   pressure [n]    in  Pa (which = 1 only, else NULL)
  *   rho_vl   [n,2]  in  A^-3 (rho_V, rho_L) from pcs_pure_vle; for which = 1 column 1 holds
  *                       rho_root from pcs_pure_liquid_density, column 0 is ignored
@@ -135,6 +138,7 @@ int pcs_pure_jacobian(int which, const double* params, const double* temp, const
  * The same Jacobian in vector-Jacobian form -- the backward pass of a property call: grad_x[i] = gout[i] * d value_i / d x_i
  * written straight into the dense gradient arrays (no [n,10] round trip through memory).
  *   gout [n] in; grad_params [n,8] (16-byte aligned), grad_temp [n], grad_pressure [n] out, each optional.
+ *   which = 3: grad_params and grad_pressure; grad_temp, if given, is zeroed (the temperature is the property, not an input).
  */
 int pcs_pure_jacobian_vjp(int which, const double* params, const double* temp, const double* pressure, const double* rho_vl,
                           const double* gout, int64_t n, double* grad_params, double* grad_temp, double* grad_pressure,
@@ -170,6 +174,24 @@ int pcs_pure_critical_point(const double* params, const double* t_init, int64_t 
  */
 int pcs_pure_critical_point_vjp(const double* params, const double* tc, const double* rhoc, int64_t n, const double* g_tc,
                                 const double* g_pc, const double* g_rhoc, double* grad_params, void* stream);
+
+/*
+ * Boiling (saturation) temperature of every parameter row at a given pressure: the T with p_sat(T) = pressure, the inverse of
+ * pcs_pure_vle / pcs_pure_vapor_pressure, with the saturated densities at that T.  Safeguarded Newton in (1/T, ln p) on fp64
+ * VLE solves, bracketed from above by the critical point (csrc/pure_boiling.hpp).  The reference has no counterpart.
+ *   params   [n,8]  in   (16-byte aligned)
+ *   pressure [n]    in   Pa
+ *   t_init   [n]    in   K, optional: first iterate instead of the corresponding-states estimate from (T_c, p_c)
+ *   temp     [n]    out  K     (optional)
+ *   rho_vl   [n,2]  out  A^-3: (rho_V, rho_L) at the returned temperature (optional)
+ *   status   [n]    out  uint8, 1 = failed: non-finite / non-physical parameters, a pressure that is non-finite, <= 0 or
+ *                        >= p_c, a non-finite or non-positive t_init, the iteration cap, or a pressure so close to p_c that
+ *                        no VLE solve succeeds inside the closed bracket; outputs of such rows are 0
+ *   iters    [n]    out  int32 trial temperatures used, -1 for failed rows (optional, diagnostics)
+ * One kernel, no workspace.  Backward pass: pcs_pure_jacobian / pcs_pure_jacobian_vjp with which = 3.
+ */
+int pcs_pure_boiling_temperature(const double* params, const double* pressure, const double* t_init, int64_t n, double* temp,
+                                 double* rho_vl, uint8_t* status, int32_t* iters, void* stream);
 
 /*
  * Binary-mixture bubble point (dew = 0: z = liquid mole fraction of component 1) or dew point

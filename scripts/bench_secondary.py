@@ -7,6 +7,8 @@ with HIP events on the launch stream, inputs resident in HBM.
   stability: tangent-plane stability analysis (pcs_mix_stability / pcs_gc_stability) of the converged bubble and dew
              feeds of configs 4 and 5 (the specified phase at the solution), batch 1e6 minus the failed rows
   critical: PcSaftPure.critical_point kernels, batch 1e6 and 1e7 (forward, forward + backward, vapor_pressure alongside)
+  boiling: PcSaftPure.boiling_temperature kernels, batch 1e6 and 1e7 (forward, forward + backward at the same process's
+           vapour pressures, vapor_pressure alongside)
 Prints one JSON object per config."""
 import json
 import os
@@ -132,3 +134,27 @@ if "critical" in which:
         it = torch.bincount(r["iters"][~failed].long()).tolist()
         print(json.dumps({"config": f"PcSaftPure critical_point batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3, "ms_forward_backward": ms_fb,
                           "ms_vapor_pressure": ms_vp, "failed": int(failed.sum()), "failed_by_class": by_class, "newton_iterations": it}))
+if "boiling" in which:
+    # boiling temperatures of the pure_batch rows at the pressures vapor_pressure gives at the batch temperatures (so every
+    # solved row has an answer: the batch temperature): forward (pcs_pure_boiling_temperature) and forward + backward
+    # (+ pcs_pure_jacobian_vjp with selector 3), next to vapor_pressure from the same process
+    for n in (1_000_000, 10_000_000):
+        P, T = pure_batch(n)
+        Pd, Td = d(P), d(T)
+        g = torch.ones(n, dtype=torch.float64, device="cuda")
+        ms_vp, vp = timed(lambda: native.pure_vapor_pressure(Pd, Td))
+        keep = torch.nonzero(~vp["status"]).view(-1)
+        Pk, Tk, pk, gk = Pd[keep].contiguous(), Td[keep].contiguous(), vp["p_sat"][keep].contiguous(), g[keep].contiguous()
+        ms, r = timed(lambda: native.pure_boiling_temperature(Pk, pk, want_iters=True), reps=3)
+
+        def fwd_bwd():
+            r = native.pure_boiling_temperature(Pk, pk)
+            return native.pure_jacobian_vjp("boiling_temperature", Pk, r["t"], None, r["rho_vl"], gk, (True, False, True))
+
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        ok = ~r["status"]
+        err = float(((r["t"][ok] / Tk[ok]) - 1.0).abs().max()) if bool(ok.any()) else float("nan")
+        it = torch.bincount(r["iters"][ok].long()).tolist()
+        print(json.dumps({"config": f"PcSaftPure boiling_temperature batch={n:.0e}", "rows": len(keep), "ms": ms, "rows_per_s": len(keep) / ms * 1e3,
+                          "ms_forward_backward": ms_fb, "ms_vapor_pressure": ms_vp, "failed": int(r["status"].sum()),
+                          "max_rel_round_trip": err, "outer_iterations": it}))
