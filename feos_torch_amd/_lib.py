@@ -40,6 +40,8 @@ SIGNATURES = {
     "pcs_pure_critical_point": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_critical_point_vjp": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_boiling_temperature": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pcs_pure_enthalpy_of_vaporization": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pcs_pure_enthalpy_of_vaporization_vjp": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcs_mix_workspace_bytes": (_i64, [_i64]),
     "pcs_mix_bubble_dew": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_mix_jacobian": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),

@@ -15,7 +15,9 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_C
            # critical points: strict IEEE semantics like pure_robust.hip (neither RELAXED nor REASSOC), csrc/pure_critical.hpp
            ("pure_critical.hip", "pure_critical.o", []),
            # boiling temperatures: strict IEEE as well (bracketing and failure detection), no fp32 pre-solve, csrc/pure_boiling.hpp
-           ("pure_boiling.hip", "pure_boiling.o", [])]
+           ("pure_boiling.hip", "pure_boiling.o", []),
+           # enthalpies of vaporization and their saturation-line gradients: strict IEEE, no fp32 pre-solve, csrc/pure_enthalpy.hpp
+           ("pure_enthalpy.hip", "pure_enthalpy.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,

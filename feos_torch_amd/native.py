@@ -312,6 +312,40 @@ def pure_boiling_temperature(parameters, pressure, initial_temperature=None, wan
     return {"t": t, "rho_vl": rho_vl, "status": status.view(torch.bool), "iters": iters}
 
 
+def pure_enthalpy_of_vaporization(parameters, temperature, want_rho_vl=False):
+    """Enthalpy of vaporization of every parameter row at `temperature` [K] (pcs_pure_enthalpy_of_vaporization).
+    -> dict(dh [kJ/mol], status bool (True = failed)[, rho_vl [n,2] A^-3 at the converged equilibrium])."""
+    device = _device_of(parameters)
+    parameters = _prep(parameters, device, (8,))
+    temperature = _prep(temperature, device)
+    n = parameters.shape[0]
+    _same_rows(n, temperature=temperature)
+    dh = _new(device, n)
+    rho_vl = _new(device, (n, 2)) if want_rho_vl else None
+    status = _new(device, n, dtype=torch.uint8)
+    _call(device, "pcs_pure_enthalpy_of_vaporization", parameters, temperature, n, dh, rho_vl, status)
+    out = {"dh": dh, "status": status.view(torch.bool)}
+    if want_rho_vl:
+        out["rho_vl"] = rho_vl
+    return out
+
+
+def pure_enthalpy_of_vaporization_vjp(parameters, temperature, rho_vl, gout, needs=(True, True)):
+    """Backward pass of pure_enthalpy_of_vaporization on solved rows: (g_params [n,8] or None, g_temp [n] or None) =
+    gout * d dh / d(parameters, T) along the saturation line (pcs_pure_enthalpy_of_vaporization_vjp)."""
+    device = _device_of(rho_vl)
+    parameters = _prep(parameters, device, (8,))
+    temperature = _prep(temperature, device)
+    rho_vl = _prep(rho_vl, device, (2,))
+    gout = _prep(gout, device)
+    n = parameters.shape[0]
+    _same_rows(n, temperature=temperature, rho_vl=rho_vl, gout=gout)
+    gp = _new(device, (n, 8)) if needs[0] else None
+    gt = _new(device, n) if needs[1] else None
+    _call(device, "pcs_pure_enthalpy_of_vaporization_vjp", parameters, temperature, rho_vl, n, gout, gp, gt)
+    return gp, gt
+
+
 def pure_critical_point(params, initial_temperature=None, want_iters=False):
     """Critical point of every parameter row (pcs_pure_critical_point).
     -> dict(t_c [K], p_c [Pa], rho_c [kmol/m3], status bool (True = failed), iters int32 or None)."""

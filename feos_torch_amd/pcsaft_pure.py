@@ -145,6 +145,46 @@ class _PureCritical(torch.autograd.Function):
         return gp.to(ctx.in_device), None
 
 
+class _PureEnthalpy(torch.autograd.Function):
+    """dh[n_ok], nans[n], plan = enthalpy_of_vaporization(parameters[n,8], temperature[n])
+
+    One solve, one compaction plan (its 4-byte count is the call's only host synchronisation); the backward pass is the
+    implicit-function kernel on the converged rows (pcs_pure_enthalpy_of_vaporization_vjp), dropped rows receive zero gradient."""
+
+    @staticmethod
+    def forward(ctx, parameters, temperature):
+        dev = native._device_of(parameters)
+        par = native._prep(parameters, dev, (8,))
+        T = native._prep(temperature, dev)
+        needs = tuple(ctx.needs_input_grad[0:2])
+        r = native.pure_enthalpy_of_vaporization(par, T, want_rho_vl=any(needs))
+        comp = native.Compaction(r["status"])
+        dh = comp.gather(r["dh"])
+        if any(needs):
+            ctx.save_for_backward(comp.gather(par), comp.gather(T), comp.gather(r["rho_vl"]))
+            ctx.comp = comp
+        ctx.needs = needs
+        ctx.set_materialize_grads(False)
+        ctx.in_devices = (parameters.device, temperature.device)
+        return (*_shell.finish(ctx, parameters.device, [dh], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_dh, _g_nans, _g_plan):
+        if g_dh is None or not any(ctx.needs):
+            return None, None
+        par, T, rho_vl = ctx.saved_tensors
+        comp = ctx.comp
+        shapes = ((comp.n, 8), (comp.n,))
+        if comp.n_ok == 0:
+            return tuple(torch.zeros(s, dtype=torch.float64, device=d) if need else None
+                         for s, d, need in zip(shapes, ctx.in_devices, ctx.needs))
+        grads = native.pure_enthalpy_of_vaporization_vjp(par, T, rho_vl, g_dh.to(comp.device).contiguous(), ctx.needs)
+        if not comp.all_ok:
+            grads = [None if g is None else comp.expand(g) for g in grads]
+        return tuple(None if g is None else g.to(d) for g, d in zip(grads, ctx.in_devices))
+
+
 class PcSaftPure(_shell.Reducible):
     def __init__(self, parameters):
         """parameters: [N, 8] float64 — m, sigma, epsilon_k, mu, kappa_ab, epsilon_k_ab, na, nb
@@ -227,6 +267,19 @@ class PcSaftPure(_shell.Reducible):
         if initial_temperature is not None:
             initial_temperature = torch.as_tensor(initial_temperature, dtype=torch.float64)
         return self._property("boiling_temperature", initial_temperature, pressure)
+
+    def enthalpy_of_vaporization(self, temperature):
+        """(nans, dh_vap [kJ/mol]) at T [K]: dh_vap = T (v_V - v_L) dp_sat/dT at the saturated densities of T, solved and
+        evaluated in one kernel (csrc/pure_enthalpy.hpp).  Values for the converged rows only; a row fails where `vapor_pressure`
+        fails: every T >= T_c (and part of the rows on the last 0.05 % of the saturation line below it), a
+        temperature that is non-positive or non-finite.  Differentiable w.r.t. the parameters and the temperature ALONG the
+        saturation line: the response of both saturated densities is carried (implicit-function theorem on equal pressure and
+        chemical potential), since dh_vap, unlike p_sat, is not stationary in them.
+        Not part of the reference's class."""
+        temperature = torch.as_tensor(temperature, dtype=torch.float64)
+        dh, nans, comp = _PureEnthalpy.apply(self._par, temperature)
+        self._reduce(comp)
+        return nans, dh
 
     def _reduce(self, comp):  # `reduce(nans)` (:235-243) is _shell.Reducible's
         if not comp.all_ok:

@@ -194,6 +194,38 @@ int pcs_pure_boiling_temperature(const double* params, const double* pressure, c
                                  double* rho_vl, uint8_t* status, int32_t* iters, void* stream);
 
 /*
+ * Enthalpy of vaporization of every parameter row at a given temperature, with the saturated densities at that T:
+ *   dh_vap = T (v_V - v_L) dp_sat/dT = R T [s(rho_L) - s(rho_V)],  s = T d(a/rho)/dT + a/rho + ln rho   (csrc/pure_enthalpy.hpp),
+ * on an all-fp64 VLE solve whose densities are converged to rounding (dh_vap is first order in their error).  The reference
+ * has no counterpart.
+ *   params   [n,8]  in   (16-byte aligned)
+ *   temp     [n]    in   K
+ *   dh       [n]    out  kJ/mol  (optional)
+ *   rho_vl   [n,2]  out  A^-3: (rho_V, rho_L) at temp (optional)
+ *   status   [n]    out  uint8, 1 = failed: non-finite / non-physical parameters, a temperature that is non-finite or <= 0,
+ *                        no vapour-liquid equilibrium (every T >= T_c), or a result that is non-finite or <= 0; outputs of
+ *                        such rows are 0
+ * One kernel, no workspace.
+ */
+int pcs_pure_enthalpy_of_vaporization(const double* params, const double* temp, int64_t n, double* dh, double* rho_vl,
+                                      uint8_t* status, void* stream);
+
+/*
+ * Backward pass of pcs_pure_enthalpy_of_vaporization on solved rows: the TOTAL derivative of dh_vap along the saturation line
+ * (the densities respond to the parameters and the temperature; implicit-function theorem on equal pressure and chemical
+ * potential in adjoint form, csrc/pure_enthalpy.hpp), times the cotangent.
+ *   params   [n,8]  in   (16-byte aligned)
+ *   temp     [n]    in   K
+ *   rho_vl   [n,2]  in   A^-3, the densities the forward call returned
+ *   g_dh     [n]    in   cotangent of dh [kJ/mol]
+ *   g_params [n,8]  out  g_dh * d dh / d parameters  (optional, 16-byte aligned)
+ *   g_temp   [n]    out  g_dh * d dh / dT [kJ/mol/K] (optional)
+ * Rows that are not a converged equilibrium (rho_vl = 0 of a failed row) give non-finite numbers: mask by status.
+ */
+int pcs_pure_enthalpy_of_vaporization_vjp(const double* params, const double* temp, const double* rho_vl, int64_t n,
+                                          const double* g_dh, double* g_params, double* g_temp, void* stream);
+
+/*
  * Binary-mixture bubble point (dew = 0: z = liquid mole fraction of component 1) or dew point
  * (dew = 1: z = vapour mole fraction of component 1) at fixed temperature.
  * Replaces PcSaft.bubble_point / PcSaft.dew_point(parameters[N,2,8], kij[N,2], temperature[N],

@@ -9,6 +9,8 @@ with HIP events on the launch stream, inputs resident in HBM.
   critical: PcSaftPure.critical_point kernels, batch 1e6 and 1e7 (forward, forward + backward, vapor_pressure alongside)
   boiling: PcSaftPure.boiling_temperature kernels, batch 1e6 and 1e7 (forward, forward + backward at the same process's
            vapour pressures, vapor_pressure alongside)
+  enthalpy: PcSaftPure.enthalpy_of_vaporization kernels, batch 1e6 and 1e7 (forward, forward + backward, vapor_pressure and
+            the all-fp64 VLE solve pcs_pure_vle_fp64 alongside, failed rows by class)
 Prints one JSON object per config."""
 import json
 import os
@@ -158,3 +160,28 @@ if "boiling" in which:
         print(json.dumps({"config": f"PcSaftPure boiling_temperature batch={n:.0e}", "rows": len(keep), "ms": ms, "rows_per_s": len(keep) / ms * 1e3,
                           "ms_forward_backward": ms_fb, "ms_vapor_pressure": ms_vp, "failed": int(r["status"].sum()),
                           "max_rel_round_trip": err, "outer_iterations": it}))
+if "enthalpy" in which:
+    # enthalpies of vaporization of the pure_batch rows at the batch temperatures: forward (pcs_pure_enthalpy_of_vaporization
+    # with the densities the backward pass needs) and forward + backward (+ pcs_pure_enthalpy_of_vaporization_vjp), next to
+    # vapor_pressure and the all-fp64 VLE solve (the forward pass is that solve plus the polish and two tangent evaluations)
+    for n in (1_000_000, 10_000_000):
+        P, T = pure_batch(n)
+        Pd, Td = d(P), d(T)
+        g = torch.ones(n, dtype=torch.float64, device="cuda")
+        ms_vp, vp = timed(lambda: native.pure_vapor_pressure(Pd, Td))
+        ms_vle, _ = timed(lambda: native.pure_vle(Pd, Td, want_p=True, want_rho_vl=True, all_fp64=True))
+        ms, r = timed(lambda: native.pure_enthalpy_of_vaporization(Pd, Td, want_rho_vl=True), reps=3)
+
+        def fwd_bwd():
+            r = native.pure_enthalpy_of_vaporization(Pd, Td, want_rho_vl=True)
+            return native.pure_enthalpy_of_vaporization_vjp(Pd, Td, r["rho_vl"], g)
+
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        failed = r["status"]
+        polar, assoc = Pd[:, 3] != 0, Pd[:, 4] != 0
+        by_class = {name: int((failed & (polar == a) & (assoc == b)).sum())
+                    for name, a, b in (("plain", False, False), ("polar", True, False), ("assoc", False, True), ("polar+assoc", True, True))}
+        print(json.dumps({"config": f"PcSaftPure enthalpy_of_vaporization batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_forward_backward": ms_fb, "ms_vapor_pressure": ms_vp, "ms_vle_fp64": ms_vle, "failed": int(failed.sum()),
+                          "failed_by_class": by_class, "failed_vapor_pressure": int(vp["status"].sum()),
+                          "failed_here_only": int((failed & ~vp["status"]).sum())}))
