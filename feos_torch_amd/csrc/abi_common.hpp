@@ -38,6 +38,15 @@ inline int enter(int64_t n, bool required_present, const char* null_message) {
     return GO_ON;
 }
 
+// 0, or the error "<entry>: <what> must be 16-byte aligned" when one of the pointers is not (the kernels move parameter and
+// gradient rows as double2; a null pointer passes)
+template <class... P>
+inline int aligned16(const char* entry, const char* what, const P*... ptrs) {
+    if (((reinterpret_cast<uintptr_t>(ptrs) | ...) & 15) == 0) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: %s must be 16-byte aligned", entry, what);
+    return 2;
+}
+
 // End of every launch sequence: 0, or the pending launch error under the name `what`
 inline int launched(const char* what) {
     hipError_t e = hipGetLastError();

@@ -274,6 +274,13 @@ template <class T, int N> PCS_DEV DN<T, N> d_log(const DN<T, N>& a) { return a.c
 template <class T, int N> PCS_DEV DN<T, N> d_exp(const DN<T, N>& a) { T e = d_exp(a.v); return a.chain(e, e); }
 template <class T, int N> PCS_DEV DN<T, N> d_sqrt(const DN<T, N>& a) { T s = d_sqrt(a.v); return a.chain(s, 0.5 * d_recip(s)); }
 template <class T, int N> PCS_DEV DN<T, N> d_cbrt(const DN<T, N>& a) { T s = d_cbrt(a.v); return a.chain(s, s * d_recip(a.v) * (1.0 / 3.0)); }
+// Input number k of a derivative pass that carries the directions d0 .. d0 + N - 1: its value, and the unit tangent where k
+// is one of them.
+template <int N> PCS_DEV void seed_unit(DN<double, N>& x, double value, int d0, int k) {
+    x.v = value;
+#pragma unroll
+    for (int j = 0; j < N; j++) x.e[j] = (d0 + j == k) ? 1.0 : 0.0;
+}
 
 // =========================================================================================
 // D3<T>: value + 1st + 2nd + 3rd derivative along ONE direction (the critical-point solver: with T = DN<double,2>

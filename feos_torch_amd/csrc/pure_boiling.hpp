@@ -14,9 +14,9 @@
 //            warm-started from the densities of the last solved trial when that lies within BOIL_WARM_DT of T, otherwise
 //            -- and whenever the warm iteration does not end on an acceptable state -- the full fp64 solve: vle_fast<false>,
 //            and the per-lane vle_robust on the lanes it hands on.  Tolerances: those of the density outputs of
-//            pcs_pure_vle (liquid step 1e-8, vapour step 1e-6, update applied).
+//            pcs_pure_vle (TOL_L_RHO, TOL_V_RHO, pure_solver.hpp: liquid step 1e-8, vapour step 1e-6, update applied).
 //   slope    d ln p* / dT at fixed densities is the Clapeyron slope (p* is stationary in both densities at equilibrium):
-//            one DN<double,1> temperature tangent through pure_coef and pure_a at both densities (boil_dlnp_dT).
+//            one temperature tangent at both densities (pure_a_dT, pure_solver.hpp) in boil_dlnp_dT.
 //   bracket  T_lo = highest trial with p_sat < p_spec, T_hi = lowest trial with p_sat > p_spec or without an equilibrium.
 //            Trials stay strictly inside the known bounds, so every trial tightens one of them.  A Newton iterate outside
 //            (or none: no equilibrium at the trial) is replaced by the midpoint in 1/T; with one bound missing it is
@@ -45,7 +45,6 @@ constexpr double BOIL_MAX_RATIO = 2.0;
 constexpr double BOIL_STEP_DOWN = 1.1;  // no equilibrium and no lower bound yet: T <- T / BOIL_STEP_DOWN
 constexpr double BOIL_CLOSED = 1e-6;
 constexpr double BOIL_TOL_F = 1e-12, BOIL_TOL_F_NOISE = 1e-11, BOIL_TOL_F_PREV = 1e-8;
-constexpr double BOIL_TOL_L = 1e-8, BOIL_TOL_V = TOL_STEP;
 
 struct BoilResult {
     double T, rho_v, rho_l;  // K, A^-3
@@ -73,7 +72,7 @@ PCS_DEV bool boil_trial(const double* q, double T, bool on, bool warm, double rh
                 if (!good) {
                     active = false;
                 } else {
-                    done = (fabs(s.dl) <= BOIL_TOL_L * l_) && (fabs(s.dv) <= BOIL_TOL_V * v_);
+                    done = (fabs(s.dl) <= TOL_L_RHO * l_) && (fabs(s.dv) <= TOL_V_RHO * v_);
                     l_ = ln;
                     v_ = vn;
                     ps = s.p_corr;
@@ -93,8 +92,8 @@ PCS_DEV bool boil_trial(const double* q, double T, bool on, bool warm, double rh
     if (__ballot(full) != 0ull) {
         VleResult r;
         r.rho_v = r.rho_l = r.p_star = 0.0;
-        int st = vle_fast<false>(q, T, r, BOIL_TOL_L, BOIL_TOL_V);  // every lane of the wave; only `full` lanes use it
-        if (full && st == ST_RETRY) st = vle_robust(c, r, BOIL_TOL_L);
+        int st = vle_fast<false>(q, T, r, TOL_L_RHO, TOL_V_RHO);  // every lane of the wave; only `full` lanes use it
+        if (full && st == ST_RETRY) st = vle_robust(c, r, TOL_L_RHO);
         if (full && st == ST_OK) {
             ok = true;
             rl = r.rho_l;
@@ -106,19 +105,12 @@ PCS_DEV bool boil_trial(const double* q, double T, bool on, bool warm, double rh
 }
 
 // d ln p_sat / dT [1/K] at fixed densities, p_sat = p* T kB/A^3 with p* = -(a_V/rho_V - a_L/rho_L + ln(rho_V/rho_L)) /
-// (1/rho_V - 1/rho_L): the construction of the generic branch of pure_jacobian<0> with the temperature as only direction.
+// (1/rho_V - 1/rho_L): column 8 of the vapour-pressure Jacobian (pure_jacobian<0>, pure_jacobian.hpp) over p_sat, from the
+// temperature tangent of a alone.
 PCS_DEV double boil_dlnp_dT(const double* q, double T, double rl, double rv, double p_star) {
-    typedef DN<double, 1> G;
-    G gp[8], gT(T);
-#pragma unroll
-    for (int k = 0; k < 8; k++) gp[k] = G(q[k]);
-    gT.e[0] = 1.0;
-    PureCoef<G> c;
-    pure_coef<G>(c, gp, gT, false);
-    const G a_l = pure_a<G, G>(c, G(rl));
-    const G a_v = pure_a<G, G>(c, G(rv));
+    const TempTangent t = pure_a_dT(q, T, rl, rv);
     const double inv_v = 1.0 / rv, inv_l = 1.0 / rl;
-    const double dps = -(a_v.e[0] * inv_v - a_l.e[0] * inv_l) / (inv_v - inv_l);
+    const double dps = -(t.aT_v * inv_v - t.aT_l * inv_l) / (inv_v - inv_l);
     return 1.0 / T + dps / p_star;
 }
 
@@ -128,10 +120,8 @@ PCS_DEV int boiling_temperature(const double* par, double p_spec, double t_init,
     out.iters = 0;
     bool fail = !crit_params_ok(par) || !is_finite_bits(p_spec) || !(p_spec > 0.0);
     if (use_init && !(is_finite_bits(t_init) && t_init > 0.0)) fail = true;
-    // harmless row for the lanes that idle through the wave-uniform loops
     double q[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) q[k] = fail ? (k < 3 ? (k == 0 ? 1.0 : (k == 1 ? 3.5 : 200.0)) : 0.0) : par[k];
+    row_or_idle(q, par, fail);
     CritResult cr;
     const bool have_c = critical_point(q, 0.0, false, cr) == 0;
     double Tc = 1.28 * q[2] * pow(q[0], 0.45), rho_c = 0.0, ln_pc = 0.0;

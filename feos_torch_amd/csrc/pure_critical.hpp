@@ -58,6 +58,12 @@ PCS_DEV bool crit_params_ok(const double* par) {
     return ok;
 }
 
+// q = the row, or harmless parameters for the lanes that idle through the wave-uniform loops of a solver (fail)
+PCS_DEV void row_or_idle(double q[8], const double* par, bool fail) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) q[k] = fail ? (k < 3 ? (k == 0 ? 1.0 : (k == 1 ? 3.5 : 200.0)) : 0.0) : par[k];
+}
+
 // min over the packing-fraction grid of dp/drho at temperature T; rho_min: its minimiser.  NaN-safe: a non-finite value
 // makes the result non-finite.
 PCS_DEV double crit_min_dp(const double* par, double T, double& rho_min) {
@@ -112,10 +118,8 @@ PCS_DEV int critical_point(const double* par, double t_init, bool use_init, Crit
     out.T = out.rho = out.p = out.p3 = 0.0;
     out.iters = 0;
     bool fail = !crit_params_ok(par);
-    // harmless parameters for the lanes that idle through the wave-uniform loops
     double q[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) q[k] = fail ? (k < 3 ? (k == 0 ? 1.0 : (k == 1 ? 3.5 : 200.0)) : 0.0) : par[k];
+    row_or_idle(q, par, fail);
     double T = 0.95 * 1.28 * q[2] * pow(q[0], 0.45);
     if (use_init && !fail) {
         if (is_finite_bits(t_init) && t_init > 0.0) T = t_init; else fail = true;

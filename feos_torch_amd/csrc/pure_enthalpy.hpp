@@ -18,8 +18,8 @@
 //                until the relative step is below ENTH_TOL_POLISH (the update is applied: the square of that is left), at
 //                most ENTH_POLISH_IT; close to T_c, where dp/drho -> 0 amplifies the rounding of p, the cap ends it.
 //   solve        the fp64 VLE solve that boil_trial (pure_boiling.hpp) runs cold: vle_fast<false>, then the per-lane
-//                vle_robust on the lanes it hands on, with the density tolerances (liquid step 1e-8, vapour step 1e-6).
-//   tangent      one DN<double,1> temperature tangent through pure_coef and pure_a per phase (as boil_dlnp_dT).
+//                vle_robust on the lanes it hands on, with the density tolerances (TOL_L_RHO, TOL_V_RHO, pure_solver.hpp).
+//   tangent      one temperature tangent at both densities (pure_a_dT, pure_solver.hpp).
 //   fails        (status 1) non-finite or non-positive T, bad parameters (crit_params_ok), no equilibrium (every T >= T_c),
 //                or a result that is non-finite or <= 0.
 //   gradient     enthalpy_vjp: total derivative of dh_vap w.r.t. (8 parameters, T) along the saturation line.  The densities
@@ -44,7 +44,6 @@
 namespace pcs {
 
 constexpr double ENTH_UNIT = 1e-6 * (RHO_UNIT * P_UNIT);
-constexpr double ENTH_TOL_L = 1e-8, ENTH_TOL_V = TOL_STEP;
 constexpr int ENTH_POLISH_IT = 3;
 constexpr double ENTH_TOL_POLISH = 1e-10;
 constexpr int ENTH_DIRS = 9;  // 8 parameters, T
@@ -60,16 +59,8 @@ struct EnthalpyResult {
 
 // H = s(rho_L) - s(rho_V) at fixed densities (form (1) of the header)
 PCS_DEV double enthalpy_reduced(const double* q, double T, double rl, double rv) {
-    typedef DN<double, 1> G;
-    G gp[8], gT(T);
-#pragma unroll
-    for (int k = 0; k < 8; k++) gp[k] = G(q[k]);
-    gT.e[0] = 1.0;
-    PureCoef<G> c;
-    pure_coef<G>(c, gp, gT, false);
-    const G a_l = pure_a<G, G>(c, G(rl));
-    const G a_v = pure_a<G, G>(c, G(rv));
-    const double s_l = (T * a_l.e[0] + a_l.v) / rl, s_v = (T * a_v.e[0] + a_v.v) / rv;
+    const TempTangent t = pure_a_dT(q, T, rl, rv);
+    const double s_l = (T * t.aT_l + t.a_l) / rl, s_v = (T * t.aT_v + t.a_v) / rv;
     return (s_l - s_v) + log(rl / rv);
 }
 
@@ -77,17 +68,15 @@ PCS_DEV double enthalpy_reduced(const double* q, double T, double rl, double rv)
 PCS_DEV int enthalpy_of_vaporization(const double* par, double T_in, EnthalpyResult& out) {
     out.dh = out.rho_v = out.rho_l = 0.0;
     bool fail = !crit_params_ok(par) || !is_finite_bits(T_in) || !(T_in > 0.0);
-    // harmless row for the lanes that idle through the wave-uniform loops
     double q[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) q[k] = fail ? (k < 3 ? (k == 0 ? 1.0 : (k == 1 ? 3.5 : 200.0)) : 0.0) : par[k];
+    row_or_idle(q, par, fail);
     const double T = fail ? 150.0 : T_in;
     VleResult r;
     r.rho_v = r.rho_l = r.p_star = 0.0;
-    int st = vle_fast<false>(q, T, r, ENTH_TOL_L, ENTH_TOL_V);
+    int st = vle_fast<false>(q, T, r, TOL_L_RHO, TOL_V_RHO);
     PureCoef<double> c;
     pure_coef<double>(c, q, T, false);
-    if (st == ST_RETRY) st = vle_robust(c, r, ENTH_TOL_L);
+    if (st == ST_RETRY) st = vle_robust(c, r, TOL_L_RHO);
     if (st != ST_OK) fail = true;
     double rl = fail ? 0.4 / c.ceta : r.rho_l, rv = fail ? 1e-3 * rl : r.rho_v;
     bool conv = fail;
@@ -136,15 +125,11 @@ PCS_DEV void enthalpy_vjp(const double* par, double T, double rv, double rl, dou
         P x[8], xT;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            x[k].v.v = par[k];
+            seed_unit(x[k].v, par[k], d0, k);
             x[k].d1 = G(0.0);
-#pragma unroll
-            for (int j = 0; j < ENTH_CHUNK; j++) x[k].v.e[j] = (d0 + j == k) ? 1.0 : 0.0;
         }
-        xT.v.v = T;
+        seed_unit(xT.v, T, d0, 8);
         xT.d1 = G(1.0);
-#pragma unroll
-        for (int j = 0; j < ENTH_CHUNK; j++) xT.v.e[j] = (d0 + j == 8) ? 1.0 : 0.0;
         PureCoef<P> c;
         pure_coef<P>(c, x, xT, true);
         G H(0.0), F1(0.0), F2(0.0);

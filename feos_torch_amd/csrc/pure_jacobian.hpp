@@ -4,9 +4,13 @@
 // The reference obtains these by torch reverse mode through its Python tail
 // (feos_torch/pcsaft_pure.py:196-199, :212-215, :228-233): the densities arrive detached from
 // the Rust solver, so only the explicit dependence on parameters / T / p is differentiated.
-// Here the same partial derivatives are propagated FORWARD with DN<double,C> tangents, C
-// directions per pass, so that the whole state stays in registers (a single 10-direction pass
-// would need > 512 VGPRs for the coefficient set alone).
+// Here every property is a function of the 33 model coefficients at one or two fixed densities:
+// the coefficient adjoints da/dc_k come from closed-form evaluations in plain doubles
+// (pure_a_adjoint), and only the coefficient set itself is differentiated FORWARD, block by
+// block with just each block's inputs seeded (DN<4> / DN<5> / DN<4>), so that the whole state
+// stays in registers.  pure_derivatives_vjp (a, p, dp at a given density, no fixed-density
+// structure to exploit) carries DN tangents through the whole evaluation, JAC_CHUNK directions
+// per pass.
 #pragma once
 #include "pure_model.hpp"
 
@@ -14,7 +18,7 @@ namespace pcs {
 
 constexpr int JAC_DIRS = 10;  // 8 parameters, T, p
 constexpr int PCS_JAC_CHUNK = 2;
-constexpr int JAC_CHUNK = PCS_JAC_CHUNK;  // directions per pass
+constexpr int JAC_CHUNK = PCS_JAC_CHUNK;  // directions per pass of pure_derivatives_vjp
 
 // Adjoint of a(rho; c) with respect to the coefficient set at fixed density, in closed form (the expressions of the
 // D1s evaluation, pure_model.hpp):  g_k = da/dc_k.  Returns a.
@@ -136,8 +140,6 @@ PCS_DEV void adjoint_axpy(const PureCoef<double>& c, PureCoefAdj<double>& adj, c
 // dT/dp = 1 / g0[8]  (g0[8] = dp_sat/dT, the Clapeyron slope); T is an output here, so its own column is 0.
 template <int WHICH>
 PCS_DEV void pure_jacobian(const double par[8], double T, double p_pa, double rv, double rl, double g[JAC_DIRS], bool polish = false) {
-    typedef DN<double, JAC_CHUNK> G;
-    constexpr int NPASS = (JAC_DIRS + JAC_CHUNK - 1) / JAC_CHUNK;
     if constexpr (WHICH == 3) {
         double g0[JAC_DIRS];
         pure_jacobian<0>(par, T, 0.0, rv, rl, g0, false);
@@ -152,193 +154,115 @@ PCS_DEV void pure_jacobian(const double par[8], double T, double p_pa, double rv
         for (int k = 0; k < JAC_DIRS; k++) asm volatile("" : "+v"(g[k]));
         return;
     }
-    {
-        // Every property is  val = F(a_c(rho_V), a_c(rho_L), a'_c(rho_L); T, p)  with the densities fixed, so its parameter
-        // derivative is  sum_k abar_k dc_k/dtheta + explicit T / p terms  with the coefficient adjoints abar from closed-form
-        // evaluations in plain doubles (pure_a_adjoint); only the coefficient set itself is then differentiated forward, all
-        // nine directions (8 parameters, T) in ONE DN<9> pass over pure_coef -- the products abar_k c_k are accumulated as
-        // the coefficients appear, so the 33 x 9 tangents never sit in registers together.
-        PureCoef<double> c0;
-        pure_coef<double>(c0, par, T, true);
-        if (WHICH == 0 && polish) {
-            // densities from the pressure-only kernel (pcs_pure_vapor_pressure: ~1e-9 from the root on ordinary rows, 1e-5 close
-            // to the critical point where dp/drho -> 0): one fp64 Newton step of the coupled iteration (vle_step, quadratic)
-            // before the derivatives are taken; the pressure itself is not touched
-            const Eval l = pure_eval(c0, rl), v = pure_eval(c0, rv);
-            const VleStep s = vle_step(l, v, rl, rv);
-            if (is_finite_bits(s.dl) && is_finite_bits(s.dv) && fabs(s.dl) < 0.1 * rl && fabs(s.dv) < 0.5 * rv) {
-                rl += s.dl;
-                rv += s.dv;
-            }
+    // Every property is  val = F(a_c(rho_V), a_c(rho_L), a'_c(rho_L); T, p)  with the densities fixed, so its parameter
+    // derivative is  sum_k abar_k dc_k/dtheta + explicit T / p terms  with the coefficient adjoints abar from closed-form
+    // evaluations in plain doubles (pure_a_adjoint); only the coefficient set itself is then differentiated forward, block
+    // by block below -- the products abar_k c_k are summed per block, so the 33 x 9 tangents never sit in registers together.
+    PureCoef<double> c0;
+    pure_coef<double>(c0, par, T, true);
+    if (WHICH == 0 && polish) {
+        // densities from the pressure-only kernel (pcs_pure_vapor_pressure: ~1e-9 from the root on ordinary rows, 1e-5 close
+        // to the critical point where dp/drho -> 0): one fp64 Newton step of the coupled iteration (vle_step, quadratic)
+        // before the derivatives are taken; the pressure itself is not touched
+        const Eval l = pure_eval(c0, rl), v = pure_eval(c0, rv);
+        const VleStep s = vle_step(l, v, rl, rv);
+        if (is_finite_bits(s.dl) && is_finite_bits(s.dv) && fabs(s.dl) < 0.1 * rl && fabs(s.dv) < 0.5 * rv) {
+            rl += s.dl;
+            rv += s.dv;
         }
-        PureCoefAdj<double> adj;
-        adj.m = adj.mm1 = adj.ceta = adj.kd1 = adj.kd2 = adj.qm = adj.da = adj.na = adj.nb = 0.0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) adj.ai[k] = adj.bi[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 5; k++) adj.j1[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) adj.j2[k] = 0.0;
-        const double inv_v = 1.0 / rv, inv_l = 1.0 / rl;
-        double gT_explicit = 0.0, gP_explicit = 0.0;
-        auto value = [](double x) { return x; };
-        if (WHICH == 0) {
-            // p_sat = K (a_V/rho_V - a_L/rho_L + ln(rho_V/rho_L)) T kB/A^3,  K = -1/(1/rho_V - 1/rho_L)   (:212-215)
-            const double K = -1.0 / (inv_v - inv_l) * (T * P_UNIT);
-            PureCoefAdj<double> gg;
-            const double a_v = pure_a_adjoint<double>(c0, rv, gg);
-            adjoint_axpy(c0, adj, gg, K * inv_v, value);
-            const double a_l = pure_a_adjoint<double>(c0, rl, gg);
-            adjoint_axpy(c0, adj, gg, -K * inv_l, value);
-            gT_explicit = K * (a_v * inv_v - a_l * inv_l + log(rv * inv_l)) / T;
-        } else {
-            // liquid_density: rho - (p(rho) - p_spec)/dp (:196-199); equilibrium_liquid_density: the same with the
-            // equal-area pressure pp in place of p_spec (:228-233).  At the root the tangent of the quotient is
-            // -(dp_tan - dp_spec_tan)/dp up to the term (p - p_spec) dp_tan / dp^2, proportional to the residual the solve
-            // left at the returned density.  Measured against the exact long-double gradient (tests/test_large_parity_gpu.py,
-            // 2e5 rows): 6.6e-11 of the row's largest component for liquid_density, 1.5e-9 for equilibrium_liquid_density
-            // (asserted at 1e-8; the reference's own tests compare gradients at 1e-4).  The reference's autograd carries the term.
-            D2<double> a0 = pure_a<double, D2<double>>(c0, D2<double>(rl, 1.0, 0.0));
-            const double dp_plain = 1.0 + rl * a0.d2;
-            const double wq = -1.0 / (dp_plain * RHO_UNIT);
-            PureCoefAdj<D1s> gl;
-            pure_a_adjoint<D1s>(c0, D1s(rl, 1.0), gl);
-            // dp/dc_k = -da/dc_k + rho da'/dc_k
-            adjoint_axpy(c0, adj, gl, wq, [rl](const D1s& x) { return rl * x.d1 - x.v; });
-            if (WHICH == 1) {
-                const double p_spec = p_pa / (T * P_UNIT);
-                gP_explicit = -wq / (T * P_UNIT);
-                gT_explicit = wq * p_spec / T;
-            } else {
-                const double Kp = -1.0 / (inv_v - inv_l);
-                PureCoefAdj<double> gv;
-                pure_a_adjoint<double>(c0, rv, gv);
-                adjoint_axpy(c0, adj, gv, -wq * Kp * inv_v, value);
-                adjoint_axpy(c0, adj, gl, wq * Kp * inv_l, [](const D1s& x) { return x.v; });
-            }
-        }
-        // the coefficient set block by block, each with just its own inputs seeded (pure_model.hpp): core (m, sigma, eps, T)
-        // DN<4>, dipole polynomials (m, sigma, eps, mu, T) DN<5>, association prefactor (sigma, kappa_ab, eps_ab, T) DN<4>;
-        // the site counts enter directly
-#pragma unroll
-        for (int d = 0; d < 9; d++) g[d] = 0.0;
-        {
-            typedef DN<double, 4> G;
-            G x[4];
-            const double v[4] = {par[0], par[1], par[2], T};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                x[k].v = v[k];
-#pragma unroll
-                for (int j = 0; j < 4; j++) x[k].e[j] = (j == k) ? 1.0 : 0.0;
-            }
-            PureCoef<G> c;
-            pure_coef_core(c, x[0], x[1], x[2], d_recip(x[3]));
-            G S = c.m * adj.m + c.mm1 * adj.mm1 + c.ceta * adj.ceta + c.kd1 * adj.kd1 + c.kd2 * adj.kd2;
-#pragma unroll
-            for (int k = 0; k < 7; k++) S = S + c.ai[k] * adj.ai[k] + c.bi[k] * adj.bi[k];
-            g[0] += S.e[0]; g[1] += S.e[1]; g[2] += S.e[2]; g[8] += S.e[3];
-        }
-        if (c0.polar) {
-            typedef DN<double, 5> G;
-            G x[5];
-            const double v[5] = {par[0], par[1], par[2], par[3], T};
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                x[k].v = v[k];
-#pragma unroll
-                for (int j = 0; j < 5; j++) x[k].e[j] = (j == k) ? 1.0 : 0.0;
-            }
-            PureCoef<G> c;
-            pure_coef_dipole(c, x[0], x[1], x[2], x[3], d_recip(x[4]));
-            G S = c.qm * adj.qm;
-#pragma unroll
-            for (int k = 0; k < 5; k++) S = S + c.j1[k] * adj.j1[k];
-#pragma unroll
-            for (int k = 0; k < 4; k++) S = S + c.j2[k] * adj.j2[k];
-            g[0] += S.e[0]; g[1] += S.e[1]; g[2] += S.e[2]; g[3] += S.e[3]; g[8] += S.e[4];
-        }
-        if (c0.assoc) {
-            typedef DN<double, 4> G;
-            G x[4];
-            const double v[4] = {par[1], par[4], par[5], T};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                x[k].v = v[k];
-#pragma unroll
-                for (int j = 0; j < 4; j++) x[k].e[j] = (j == k) ? 1.0 : 0.0;
-            }
-            const G S = pure_coef_da(x[0], x[1], x[2], d_recip(x[3])) * adj.da;
-            g[1] += S.e[0]; g[4] += S.e[1]; g[5] += S.e[2]; g[8] += S.e[3];
-            g[6] += adj.na;
-            g[7] += adj.nb;
-        }
-        g[8] += gT_explicit;
-        g[9] = gP_explicit;
-        return;
     }
-    double dp_plain = 1.0;
-    if (WHICH != 0) {
-        PureCoef<double> c0;
-        pure_coef<double>(c0, par, T, true);
+    PureCoefAdj<double> adj;
+    adj.m = adj.mm1 = adj.ceta = adj.kd1 = adj.kd2 = adj.qm = adj.da = adj.na = adj.nb = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) adj.ai[k] = adj.bi[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; k++) adj.j1[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) adj.j2[k] = 0.0;
+    const double inv_v = 1.0 / rv, inv_l = 1.0 / rl;
+    double gT_explicit = 0.0, gP_explicit = 0.0;
+    auto value = [](double x) { return x; };
+    if (WHICH == 0) {
+        // p_sat = K (a_V/rho_V - a_L/rho_L + ln(rho_V/rho_L)) T kB/A^3,  K = -1/(1/rho_V - 1/rho_L)   (:212-215)
+        const double K = -1.0 / (inv_v - inv_l) * (T * P_UNIT);
+        PureCoefAdj<double> gg;
+        const double a_v = pure_a_adjoint<double>(c0, rv, gg);
+        adjoint_axpy(c0, adj, gg, K * inv_v, value);
+        const double a_l = pure_a_adjoint<double>(c0, rl, gg);
+        adjoint_axpy(c0, adj, gg, -K * inv_l, value);
+        gT_explicit = K * (a_v * inv_v - a_l * inv_l + log(rv * inv_l)) / T;
+    } else {
+        // liquid_density: rho - (p(rho) - p_spec)/dp (:196-199); equilibrium_liquid_density: the same with the
+        // equal-area pressure pp in place of p_spec (:228-233).  At the root the tangent of the quotient is
+        // -(dp_tan - dp_spec_tan)/dp up to the term (p - p_spec) dp_tan / dp^2, proportional to the residual the solve
+        // left at the returned density.  Measured against the exact long-double gradient (tests/test_large_parity_gpu.py,
+        // 2e5 rows): 6.6e-11 of the row's largest component for liquid_density, 1.5e-9 for equilibrium_liquid_density
+        // (asserted at 1e-8; the reference's own tests compare gradients at 1e-4).  The reference's autograd carries the term.
         D2<double> a0 = pure_a<double, D2<double>>(c0, D2<double>(rl, 1.0, 0.0));
-        dp_plain = 1.0 + rl * a0.d2;
-    }
-#pragma unroll 1
-    for (int pass = 0; pass < NPASS; pass++) {
-        const int d0 = pass * JAC_CHUNK;
-        G gp[8], gT, gP;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            gp[k].v = par[k];
-#pragma unroll
-            for (int j = 0; j < JAC_CHUNK; j++) gp[k].e[j] = (d0 + j == k) ? 1.0 : 0.0;
-        }
-        gT.v = T;
-        gP.v = p_pa;
-#pragma unroll
-        for (int j = 0; j < JAC_CHUNK; j++) {
-            gT.e[j] = (d0 + j == 8) ? 1.0 : 0.0;
-            gP.e[j] = (d0 + j == 9) ? 1.0 : 0.0;
-        }
-        PureCoef<G> c;
-        pure_coef<G>(c, gp, gT, true);
-        G val;
-        if (WHICH == 0) {
-            // p = -(a_V/rho_V - a_L/rho_L + ln(rho_V/rho_L)) / (1/rho_V - 1/rho_L) * T * kB/A^3   (:212-215)
-            G a_l = pure_a<G, G>(c, G(rl));
-            G a_v = pure_a<G, G>(c, G(rv));
-            double inv_v = 1.0 / rv, inv_l = 1.0 / rl;
-            G num = a_v * inv_v - a_l * inv_l + log(rv * inv_l);
-            val = (num * (-1.0 / (inv_v - inv_l))) * gT * P_UNIT;
-        } else if (WHICH == 1) {
-            // rho - (p(rho) - p_spec)/dp  (:196-199).  At the root p = p_spec, so the tangent of the quotient is
-            // -(dp_tan - dp_spec_tan)/dp up to a term proportional to the residual left by the solve (measured bound above): only a
-            // and a' need parameter tangents (D1<G>); dp/drho is a plain number from a D2<double> evaluation.
-            typedef D1<G> R1;
-            R1 r = pure_a<G, R1>(c, R1(G(rl), G(1.0)));
-            G p = rl - r.v + rl * r.d1;
-            G p_spec = gP / gT * (1.0 / P_UNIT);
-            val = (rl - (p - p_spec) * (1.0 / dp_plain)) * (1.0 / RHO_UNIT);
+        const double dp_plain = 1.0 + rl * a0.d2;
+        const double wq = -1.0 / (dp_plain * RHO_UNIT);
+        PureCoefAdj<D1s> gl;
+        pure_a_adjoint<D1s>(c0, D1s(rl, 1.0), gl);
+        // dp/dc_k = -da/dc_k + rho da'/dc_k
+        adjoint_axpy(c0, adj, gl, wq, [rl](const D1s& x) { return rl * x.d1 - x.v; });
+        if (WHICH == 1) {
+            const double p_spec = p_pa / (T * P_UNIT);
+            gP_explicit = -wq / (T * P_UNIT);
+            gT_explicit = wq * p_spec / T;
         } else {
-            // (:228-233), same argument: the equal-area pressure pp needs the values of a in both phases, the liquid
-            // pressure a and a'
-            typedef D1<G> R1;
-            R1 r = pure_a<G, R1>(c, R1(G(rl), G(1.0)));
-            G p_l = rl - r.v + rl * r.d1;
-            double inv_v = 1.0 / rv, inv_l = 1.0 / rl;
-            G a_l = r.v * inv_l;
-            G a_v = pure_a<G, G>(c, G(rv)) * inv_v;
-            G pp = (a_v - a_l + log(rv * inv_l)) * (-1.0 / (inv_v - inv_l));
-            val = (rl - (p_l - pp) * (1.0 / dp_plain)) * (1.0 / RHO_UNIT);
-        }
-#pragma unroll
-        for (int d = 0; d < JAC_DIRS; d++) {
-#pragma unroll
-            for (int j = 0; j < JAC_CHUNK; j++)
-                if (d == d0 + j && d < JAC_DIRS) g[d] = val.e[j];
+            const double Kp = -1.0 / (inv_v - inv_l);
+            PureCoefAdj<double> gv;
+            pure_a_adjoint<double>(c0, rv, gv);
+            adjoint_axpy(c0, adj, gv, -wq * Kp * inv_v, value);
+            adjoint_axpy(c0, adj, gl, wq * Kp * inv_l, [](const D1s& x) { return x.v; });
         }
     }
+    // the coefficient set block by block, each with just its own inputs seeded (pure_model.hpp): core (m, sigma, eps, T)
+    // DN<4>, dipole polynomials (m, sigma, eps, mu, T) DN<5>, association prefactor (sigma, kappa_ab, eps_ab, T) DN<4>;
+    // the site counts enter directly
+#pragma unroll
+    for (int d = 0; d < 9; d++) g[d] = 0.0;
+    {
+        typedef DN<double, 4> G;
+        G x[4];
+        const double v[4] = {par[0], par[1], par[2], T};
+#pragma unroll
+        for (int k = 0; k < 4; k++) seed_unit(x[k], v[k], 0, k);
+        PureCoef<G> c;
+        pure_coef_core(c, x[0], x[1], x[2], d_recip(x[3]));
+        G S = c.m * adj.m + c.mm1 * adj.mm1 + c.ceta * adj.ceta + c.kd1 * adj.kd1 + c.kd2 * adj.kd2;
+#pragma unroll
+        for (int k = 0; k < 7; k++) S = S + c.ai[k] * adj.ai[k] + c.bi[k] * adj.bi[k];
+        g[0] += S.e[0]; g[1] += S.e[1]; g[2] += S.e[2]; g[8] += S.e[3];
+    }
+    if (c0.polar) {
+        typedef DN<double, 5> G;
+        G x[5];
+        const double v[5] = {par[0], par[1], par[2], par[3], T};
+#pragma unroll
+        for (int k = 0; k < 5; k++) seed_unit(x[k], v[k], 0, k);
+        PureCoef<G> c;
+        pure_coef_dipole(c, x[0], x[1], x[2], x[3], d_recip(x[4]));
+        G S = c.qm * adj.qm;
+#pragma unroll
+        for (int k = 0; k < 5; k++) S = S + c.j1[k] * adj.j1[k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) S = S + c.j2[k] * adj.j2[k];
+        g[0] += S.e[0]; g[1] += S.e[1]; g[2] += S.e[2]; g[3] += S.e[3]; g[8] += S.e[4];
+    }
+    if (c0.assoc) {
+        typedef DN<double, 4> G;
+        G x[4];
+        const double v[4] = {par[1], par[4], par[5], T};
+#pragma unroll
+        for (int k = 0; k < 4; k++) seed_unit(x[k], v[k], 0, k);
+        const G S = pure_coef_da(x[0], x[1], x[2], d_recip(x[3])) * adj.da;
+        g[1] += S.e[0]; g[4] += S.e[1]; g[5] += S.e[2]; g[8] += S.e[3];
+        g[6] += adj.na;
+        g[7] += adj.nb;
+    }
+    g[8] += gT_explicit;
+    g[9] = gP_explicit;
 }
 
 // Vector-Jacobian product of PcSaftPure.derivatives (feos_torch/pcsaft_pure.py:180-182): the outputs

@@ -17,6 +17,7 @@
 #include "block_order.hpp"
 #include "pure_solver.hpp"
 #include "pure_jacobian.hpp"
+#include "pure_stage.hpp"
 
 // This file is compiled TWICE (feos_torch_amd/build.py), with the same relaxed floating-point flags but
 //   PCS_PURE_PART = 1  with -fassociative-math -freciprocal-math: the pressure-only VLE kernel (0.783 -> 0.750 ms per 1e7 rows,
@@ -51,31 +52,8 @@ thread_local char pcs_abi::g_err[256] = "";
 
 namespace {
 
-constexpr int PCS_BLOCK = 256;
-constexpr int BLOCK = PCS_BLOCK;
-constexpr int ROW_PAD = 9;  // doubles per staged row (8 + 1 pad): bank-conflict-free per-lane reads
-
-// Cooperative, coalesced load of the workgroup's parameter rows into LDS, then one row per lane.
-// Rows past n are clamped to row n-1 (their results are never stored).
-__device__ __forceinline__ void stage_params(const double* __restrict__ params, int64_t n, int64_t row0,
-                                             double* lds, double par[8]) {
-    const int t = threadIdx.x;
-    const double2* src = reinterpret_cast<const double2*>(params);
-    const int64_t last2 = n * 4 - 1;  // index of the last double2
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int idx2 = t + k * BLOCK;  // double2 index inside the block tile: row = idx2/4, col2 = idx2%4
-        int64_t g = row0 * 4 + idx2;
-        if (g > last2) g = last2 - 3 + (idx2 & 3);  // clamp to the same columns of row n-1
-        double2 v = src[g];
-        int r = idx2 >> 2, c2 = idx2 & 3;
-        lds[r * ROW_PAD + 2 * c2] = v.x;
-        lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; k++) par[k] = lds[t * ROW_PAD + k];
-}
+constexpr int BLOCK = STAGE_BLOCK;  // workgroup size, padded row and stage_rows: pure_stage.hpp
+constexpr int ROW_PAD = STAGE_ROW_PAD;
 
 // ------------------------------------------------------------------------------------------
 // K1: pure VLE, fast path.  Rows that need the robust initialisation are appended to
@@ -120,7 +98,7 @@ __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    // cooperative, coalesced staging as stage_params, plus T (rows past n clamp to row n-1; never stored).  Written out,
+    // cooperative, coalesced staging as stage_rows (pure_stage.hpp), plus T (rows past n clamp to row n-1; never stored).  Written out,
     // like the result stores below: behind a shared helper the compiler schedules these four kernels differently
     {
         const double2* src = reinterpret_cast<const double2*>(params);
@@ -255,16 +233,16 @@ __global__ __launch_bounds__(BLOCK, K2_WAVES) void k_pure_liquid_density(const d
                                                                uint8_t* __restrict__ status) {
     __shared__ double lds[BLOCK * ROW_PAD];
     const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    double par[8];
     // rows of the workgroup bucketed by class as in k_pure_vle (LDS counting sort): a wave mostly runs one set of
     // branches of the Helmholtz energy
     __shared__ int perm[BLOCK];
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
     block_order_reset<K1_BINS>(bins);
-    stage_params(params, n, row0, lds, par);
+    stage_rows(params, n, row0, lds);
     block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
     const int src = perm[t];
+    double par[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) par[q] = lds[src * ROW_PAD + q];
     const int64_t i = row0 + src;
@@ -298,17 +276,12 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives(const double* __rest
                                                             const double* __restrict__ rho_in, int64_t n,
                                                             double* __restrict__ a, double* __restrict__ p,
                                                             double* __restrict__ dp) {
-    __shared__ double lds[BLOCK * ROW_PAD];
-    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    const int64_t i = row0 + threadIdx.x;
-    const bool live = i < n;
-    double par[8];
-    stage_params(params, n, row0, lds, par);
-    const int64_t ii = live ? i : n - 1;
+    const LaneRow row = stage_lane_row(params, n);
+    const int64_t i = row.i, ii = row.ii;
     PureCoef<double> c;
-    pure_coef<double>(c, par, temp[ii], false);
+    pure_coef<double>(c, row.par, temp[ii], false);
     Eval e = pure_eval(c, rho_in[ii]);
-    if (!live) return;
+    if (!row.live) return;
     if (a) a[i] = e.a;
     if (p) p[i] = e.p;
     if (dp) dp[i] = e.dp;
@@ -355,7 +328,7 @@ __global__ __launch_bounds__(BLOCK, K4_WAVES) void k_pure_jacobian(const double*
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
     if (BUCKET) block_order_reset<K1_BINS>(bins);
-    stage_params(params, n, row0, lds, par);
+    stage_rows(params, n, row0, lds, par);
     int src = t;
     if (BUCKET) {
         block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
@@ -399,16 +372,11 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives_vjp(const double* __
                                                                 const double* __restrict__ g_dp,
                                                                 double* __restrict__ grad_params, double* __restrict__ grad_temp,
                                                                 double* __restrict__ grad_rho) {
-    __shared__ double lds[BLOCK * ROW_PAD];
-    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    const int64_t i = row0 + threadIdx.x;
-    const bool live = i < n;
-    double par[8];
-    stage_params(params, n, row0, lds, par);
-    const int64_t ii = live ? i : n - 1;
+    const LaneRow row = stage_lane_row(params, n);
+    const int64_t i = row.i, ii = row.ii;
     double g[VJP_DIRS];
-    pure_derivatives_vjp(par, temp[ii], rho_in[ii], g_a ? g_a[ii] : 0.0, g_p ? g_p[ii] : 0.0, g_dp ? g_dp[ii] : 0.0, g);
-    if (!live) return;
+    pure_derivatives_vjp(row.par, temp[ii], rho_in[ii], g_a ? g_a[ii] : 0.0, g_p ? g_p[ii] : 0.0, g_dp ? g_dp[ii] : 0.0, g);
+    if (!row.live) return;
     if (grad_params) {
 #pragma unroll
         for (int k = 0; k < 8; k++) grad_params[8 * i + k] = g[k];
@@ -567,7 +535,7 @@ static int launch_pure_jacobian(const char* entry, int which, const double* para
     const int polish = (which & PCS_JAC_POLISH) ? 1 : 0;
     which &= ~PCS_JAC_POLISH;
     if (which == 1 && !pressure) return fail_msg(entry, "pressure required for liquid_density");
-    if ((reinterpret_cast<uintptr_t>(grad_params) & 15) != 0) return fail_msg(entry, "grad_params must be 16-byte aligned");
+    if (int e = aligned16(entry, "grad_params", grad_params)) return e;
     const unsigned grid = grid_for(n, BLOCK);
     switch (which) {
         case 0: hipLaunchKernelGGL(k_pure_jacobian<0>, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, rho_vl, n, jac, gout, grad_params, grad_temp, grad_pressure, polish); break;

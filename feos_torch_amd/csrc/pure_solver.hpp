@@ -523,4 +523,27 @@ PCS_DEV int vle_robust(const PureCoef<double>& c, VleResult& out, double tol_l =
     return ST_FAILED;
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the strict-IEEE units without an fp32 pre-solve share (pure_boiling.hpp, pure_enthalpy.hpp)
+// ---------------------------------------------------------------------------------------------
+// tolerances of the density outputs of pcs_pure_vle: relative liquid / vapour step, update applied
+constexpr double TOL_L_RHO = 1e-8, TOL_V_RHO = TOL_STEP;
+
+// a and a_T = da/dT at the densities rl and rv: one DN<double,1> temperature tangent through pure_coef and pure_a
+struct TempTangent {
+    double a_l, aT_l, a_v, aT_v;
+};
+PCS_DEV TempTangent pure_a_dT(const double* q, double T, double rl, double rv) {
+    typedef DN<double, 1> G;
+    G gp[8], gT(T);
+#pragma unroll
+    for (int k = 0; k < 8; k++) gp[k] = G(q[k]);
+    gT.e[0] = 1.0;
+    PureCoef<G> c;
+    pure_coef<G>(c, gp, gT, false);
+    const G a_l = pure_a<G, G>(c, G(rl));
+    const G a_v = pure_a<G, G>(c, G(rv));
+    return {a_l.v, a_l.e[0], a_v.v, a_v.e[0]};
+}
+
 }  // namespace pcs

@@ -210,8 +210,24 @@ def test_edge_rows_shapes_and_initial_temperature(amd):
     assert np.array_equal(nans.numpy(), bad) and t_c.shape == p_c.shape == rho_c.shape == (694,)
     assert eos.parameters.shape == (694, 8) and np.array_equal(eos.parameters, P[~bad])
     assert np.array_equal(t_c.numpy(), r["t_c"][~bad])
-    # a supplied start within +-30 % of T_c: same point
     G = P[~bad]
+    # partial workgroups (idle lanes repeat the last row): 1 and 257 rows alone equal the same rows of a 512-row call bit
+    # for bit, solve and gradient
+    dev = torch.device("cuda:0")
+    full = _solve(G[:512])
+    tc, rc = torch.from_numpy(full["t_c"]).to(dev), torch.from_numpy(full["rho_c"]).to(dev)
+    w = torch.linspace(0.5, 1.5, 512, dtype=f64, device=dev)
+    grad = lambda m: native.pure_critical_point_vjp(torch.from_numpy(G[:m]).to(dev), tc[:m], rc[:m], g_tc=w[:m], g_pc=1e-6 * w[:m],
+                                                     g_rhoc=-3.0 * w[:m])
+    g_full = grad(512)
+    assert not full["status"].any() and torch.isfinite(g_full).all().item()
+    for m in (1, 257):
+        part = _solve(G[:m])
+        for k in ("t_c", "p_c", "rho_c"):
+            assert np.array_equal(part[k].view(np.int64), full[k][:m].view(np.int64)), (m, k)
+        assert not part["status"].any()
+        assert torch.equal(grad(m).view(torch.int64), g_full[:m].view(torch.int64)), m
+    # a supplied start within +-30 % of T_c: same point
     t0 = r["t_c"][~bad] * np.random.default_rng(5).uniform(0.7, 1.3, len(G))
     nans2, t2, p2, rho2 = amd.PcSaftPure(torch.from_numpy(G)).critical_point(initial_temperature=torch.from_numpy(t0))
     assert not nans2.any().item()

@@ -170,6 +170,13 @@ def test_schedule_independence(ctx):
         assert np.array_equal(r["status"].cpu().numpy(), b["status"][idx]), m
         assert np.array_equal(r["dh"].cpu().numpy().view(np.int64), b["dh"][idx].view(np.int64)), m
         assert np.array_equal(r["rho_vl"].cpu().numpy().view(np.int64), b["rho_vl"][idx].view(np.int64)), m
+    # the gradient kernel too: prefixes of a 512-row call alone (partial workgroups: idle lanes repeat the last row)
+    idx = ctx.perm[~b["status"][ctx.perm]][:512]
+    full = _vjp(ctx, ctx.g.P[idx], ctx.g.T[idx], b["rho_vl"][idx])
+    assert len(idx) == 512 and torch.isfinite(full).all().item()
+    for m in sg.PREFIXES:
+        part = _vjp(ctx, ctx.g.P[idx[:m]], ctx.g.T[idx[:m]], b["rho_vl"][idx[:m]])
+        assert torch.equal(part.view(torch.int64), full[:m].view(torch.int64)), m
     # the value does not depend on whether the densities are requested
     r = native.pure_enthalpy_of_vaporization(ctx.d(ctx.g.P), ctx.d(ctx.g.T))
     assert "rho_vl" not in r and np.array_equal(r["dh"].cpu().numpy().view(np.int64), a["dh"].view(np.int64))
