@@ -642,4 +642,121 @@ void orc_gc_bubble_dew_grad(int S, const double* seg, const double* kab, const d
     }
 }
 
+// GcPcSaftMix.derivatives in long double with the safeguarded association iterations (and the cancellation-free site
+// fractions the long-double instantiations select): the exact values of the model, rounded to double at the very end.
+int orc_gc_derivatives_ld(int S, const double* seg, const double* kab, const double* counts, const double* bonds,
+                          const double* phi, const double* T, const double* rho, int64_t n, double* a, double* p,
+                          double* mu, double* v) {
+    int bad = 0;
+#pragma omp parallel for schedule(static) reduction(| : bad)
+    for (int64_t i = 0; i < n; i++) {
+        typedef long double F;
+        GcRow r;
+        if (!gc_row(r, S, seg, kab, counts, bonds, phi, i)) { bad |= 1; continue; }
+        r.robust = true;
+        GcModel<F> model{r};
+        F rr[2] = {F(rho[2 * i]), F(rho[2 * i + 1])}, aa, pp, m2[2], v2[2];
+        derivatives_generic<F>(model, F(T[i]), rr, aa, pp, m2, v2);
+        a[i] = double(aa); p[i] = double(pp);
+        for (int k = 0; k < 2; k++) { mu[2 * i + k] = double(m2[k]); v[2 * i + k] = double(v2[k]); }
+    }
+    return bad;
+}
+
+// Exact gradient of L_i = ga a + gp p + gmu . mu + gv . v (GcPcSaftMix.derivatives at one state point per row), long double
+// throughout, rounded to double only when the results are stored:
+//   grad_row [n,5]  dL_i/d(phi_0, phi_1, T, rho_0, rho_1)             nested duals: HyperDual<DualN<long double, 6>, 3>
+//   grad_kab [S,S]  sum_i dL_i/d k_ab (symmetric pair, both entries)   nested duals, one pair of the row per pass
+//   grad_seg [S,8]  sum_i dL_i/d segment table                        central differences, relative steps 1e-5 and 5e-6,
+//                                                                     Richardson-extrapolated
+// The segment table of gc_pcsaft.hpp is held in plain doubles (its sqrt(eps_a eps_b) must stay a number: epsilon_k = 0 of '>C<'
+// has no dual square root), so table directions cannot be seeded; everything else is.  Table entries that are structurally zero
+// (mu, kappa_ab, epsilon_k_ab, na, nb = 0; epsilon_k = 0) and segments no row uses stay 0.  The row sums are carried in
+// long double.
+int orc_gc_derivatives_vjp_exact(int S, const double* seg, const double* kab, const double* counts, const double* bonds,
+                                 const double* phi, const double* T, const double* rho, int64_t n, const double* ga,
+                                 const double* gp, const double* gmu, const double* gv, double* grad_row, double* grad_seg,
+                                 double* grad_kab) {
+    typedef long double F;
+    int bad = 0;
+    std::vector<F> sum_seg((size_t)S * 8, F(0)), sum_kab((size_t)S * S, F(0));
+#pragma omp parallel reduction(| : bad)
+    {
+        std::vector<F> my_seg((size_t)S * 8, F(0)), my_kab((size_t)S * S, F(0));
+        std::vector<double> tab(seg, seg + (size_t)S * 8);
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t i = 0; i < n; i++) {
+            GcRow r;
+            if (!gc_row(r, S, seg, kab, counts, bonds, phi, i)) { bad |= 1; continue; }
+            r.robust = true;
+            const F wa = ga[i], wp = gp[i], wm0 = gmu[2 * i], wm1 = gmu[2 * i + 1], wv0 = gv[2 * i], wv1 = gv[2 * i + 1];
+            // ---- phi, T, rho and k_ab: duals.  Directions: 0 = k_ab pair of the pass, 1, 2 = phi, 3 = T, 4, 5 = rho
+            typedef DualN<F, 6> G;
+            const double* c0 = r.counts;
+            const double* c1 = r.counts + S;
+            bool first = true;
+            auto pass = [&](int ka, int kb) {
+                GcGradModel<G> model{r, G::var(F(kab[ka * S + kb]), 0), {G::var(F(phi[2 * i]), 1), G::var(F(phi[2 * i + 1]), 2)}, ka, kb};
+                G rr[2] = {G::var(F(rho[2 * i]), 4), G::var(F(rho[2 * i + 1]), 5)}, aa, pp, m2[2], v2[2];
+                derivatives_generic<G>(model, G::var(F(T[i]), 3), rr, aa, pp, m2, v2);
+                F e[6];
+                for (int k = 0; k < 6; k++)
+                    e[k] = wa * aa.eps[k] + wp * pp.eps[k] + wm0 * m2[0].eps[k] + wm1 * m2[1].eps[k] + wv0 * v2[0].eps[k] + wv1 * v2[1].eps[k];
+                if (first) {
+                    for (int k = 0; k < 5; k++) grad_row[5 * i + k] = double(e[1 + k]);
+                    first = false;
+                }
+                return e[0];
+            };
+            for (int a = 0; a < S; a++)
+                for (int b = 0; b <= a; b++) {
+                    if (!((c0[a] != 0.0 && c1[b] != 0.0) || (c0[b] != 0.0 && c1[a] != 0.0))) continue;
+                    const F g = pass(a, b);
+                    my_kab[(size_t)a * S + b] += g;
+                    if (a != b) my_kab[(size_t)b * S + a] += g;
+                }
+            if (first) pass(0, 0);  // a row without a segment pair (cannot happen: every molecule has a segment)
+            // ---- segment table: Richardson-extrapolated central differences of the long-double evaluation
+            auto value = [&]() {
+                GcRow q;
+                gc_row(q, S, tab.data(), kab, counts, bonds, phi, i);
+                q.robust = true;
+                GcModel<F> model{q};
+                F rr[2] = {F(rho[2 * i]), F(rho[2 * i + 1])}, aa, pp, m2[2], v2[2];
+                derivatives_generic<F>(model, F(T[i]), rr, aa, pp, m2, v2);
+                return wa * aa + wp * pp + wm0 * m2[0] + wm1 * m2[1] + wv0 * v2[0] + wv1 * v2[1];
+            };
+            for (int a = 0; a < S; a++) {
+                if (c0[a] == 0.0 && c1[a] == 0.0) continue;
+                for (int k = 0; k < 8; k++) {
+                    const double x = seg[8 * a + k];
+                    if (x == 0.0) continue;
+                    F d[2], h2[2];
+                    for (int lvl = 0; lvl < 2; lvl++) {
+                        const double h = (lvl == 0 ? 1e-5 : 5e-6) * std::fabs(x);
+                        volatile double xp = x + h, xm = x - h;  // the steps actually taken are xp - x and x - xm
+                        tab[8 * a + k] = xp;
+                        const F fp = value();
+                        tab[8 * a + k] = xm;
+                        const F fm = value();
+                        const F width = F(xp) - F(xm);
+                        d[lvl] = (fp - fm) / width;
+                        h2[lvl] = width * width;
+                    }
+                    tab[8 * a + k] = x;
+                    my_seg[(size_t)8 * a + k] += (h2[0] * d[1] - h2[1] * d[0]) / (h2[0] - h2[1]);
+                }
+            }
+        }
+#pragma omp critical
+        {
+            for (size_t k = 0; k < sum_seg.size(); k++) sum_seg[k] += my_seg[k];
+            for (size_t k = 0; k < sum_kab.size(); k++) sum_kab[k] += my_kab[k];
+        }
+    }
+    for (size_t k = 0; k < sum_seg.size(); k++) grad_seg[k] = double(sum_seg[k]);
+    for (size_t k = 0; k < sum_kab.size(); k++) grad_kab[k] = double(sum_kab[k]);
+    return bad;
+}
+
 }  // extern "C"

@@ -105,6 +105,11 @@ def lib():
         _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
         L.orc_gc_derivatives.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p, _f64p, _f64p]
         L.orc_gc_derivatives.restype = _int
+        L.orc_gc_derivatives_ld.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p, _f64p]
+        L.orc_gc_derivatives_ld.restype = _int
+        L.orc_gc_derivatives_vjp_exact.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p, _f64p,
+                                                   _f64p, _f64p, _f64p]
+        L.orc_gc_derivatives_vjp_exact.restype = _int
         L.orc_gc_bubble_dew.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _f64p, _f64p, _u8p]
         L.orc_gc_bubble_dew.restype = _int
         L.orc_gc_bubble_dew_grad.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _int, _int, _f64p, _f64p]
@@ -339,15 +344,46 @@ def gc_encode(segment_records, segment_lists, bond_lists, binary_segment_records
     return {"S": S, "seg": seg, "kab": kab, "counts": counts, "bonds": bonds, "ident": ident}
 
 
-def gc_derivatives(enc, phi, T, rho, robust=False):
+def gc_derivatives(enc, phi, T, rho, robust=False, prec=0):
+    """GcPcSaftMix.derivatives: a[n], p[n], mu[n,2], v[n,2] (reduced).  prec=0: fp64; robust=False runs the association
+    sub-iterations literally as the reference does, True uses the safeguarded form.  prec=1: long double with the safeguarded
+    association and the cancellation-free site fractions (robust is implied), rounded to double: the exact values of the model."""
     phi, T, rho = _c(phi), _c(T), _c(rho)
     n = T.shape[0]
     a, p, mu, v = np.empty(n), np.empty(n), np.empty((n, 2)), np.empty((n, 2))
-    bad = lib().orc_gc_derivatives(enc["S"], _c(enc["seg"]), _c(enc["kab"]), _c(enc["counts"]), _c(enc["bonds"]), phi, T,
-                                   rho, n, int(bool(robust)), a, p, mu, v)
+    tab = (enc["S"], _c(enc["seg"]), _c(enc["kab"]), _c(enc["counts"]), _c(enc["bonds"]))
+    if prec == 1:
+        bad = lib().orc_gc_derivatives_ld(*tab, phi, T, rho, n, a, p, mu, v)
+    else:
+        bad = lib().orc_gc_derivatives(*tab, phi, T, rho, n, int(bool(robust)), a, p, mu, v)
     if bad:
         raise Exception("Only up to one associating segment per component is allowed!")
     return a, p, mu, v
+
+
+def gc_derivatives_vjp_exact(enc, phi, T, rho, ga, gp, gmu, gv):
+    """Gradient of L_i = ga_i a_i + gp_i p_i + gmu_i . mu_i + gv_i . v_i (GcPcSaftMix.derivatives) and of sum_i L_i, evaluated in
+    long double and rounded to double only on return:
+      grad_row [n,5]  dL_i/d(phi_0, phi_1, T, rho_0, rho_1),
+      grad_seg [S,8]  d sum_i L_i / d segment table, the row sum carried in long double,
+      grad_kab [S,S]  d sum_i L_i / d k_ab; an entry is the derivative w.r.t. the symmetric pair k_ab[a,b] = k_ab[b,a] (what the
+                      gradient of one binary segment record is) and is stored at both places.
+    Method: phi, T, rho and k_ab by nested duals (HyperDual over DualN<long double, 6>, one k_ab pair of the row per pass).
+    The SEGMENT TABLE by the fallback: central differences of the long-double evaluation at relative steps 1e-5 and 5e-6,
+    Richardson-extrapolated, differences and sums in long double -- oracle/gc_pcsaft.hpp keeps the table in plain doubles (its
+    sqrt(eps_a eps_b) has no dual at epsilon_k = 0 of '>C<'), so table directions cannot be seeded into it.
+    Conventions of gc_segment_grad_fd: entries whose parameter is structurally zero (mu, kappa_ab, epsilon_k_ab, na, nb = 0),
+    the epsilon_k entry of a segment with epsilon_k = 0 and segments no row uses are reported as 0 (not to be compared)."""
+    phi, T, rho = _c(phi), _c(T), _c(rho)
+    n = T.shape[0]
+    ga, gp, gmu, gv = _c(ga, (n,)), _c(gp, (n,)), _c(gmu, (n, 2)), _c(gv, (n, 2))
+    S = enc["S"]
+    grow, gseg, gkab = np.empty((n, 5)), np.empty((S, 8)), np.empty((S, S))
+    bad = lib().orc_gc_derivatives_vjp_exact(S, _c(enc["seg"]), _c(enc["kab"]), _c(enc["counts"]), _c(enc["bonds"]), phi, T, rho, n,
+                                             ga, gp, gmu, gv, grow, gseg, gkab)
+    if bad:
+        raise Exception("Only up to one associating segment per component is allowed!")
+    return grow, gseg, gkab
 
 
 def gc_bubble_dew(enc, phi, T, z, p_init, dew, prec=1):

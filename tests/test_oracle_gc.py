@@ -3,7 +3,11 @@
 of tests/test_gc_pcsaft.py:17-49 (reference tolerance abs 1e-14 / 1e-11, :122-127), the
 n-butane/propane bubble and dew points with dp/dk_ab (:130-222, abs 1e-8 Pa / abs 1) and 48
 seeded random rows.  The segment table tests/data/sauer2014_hetero.json is the reference's own
-test data file (tests/sauer2014_hetero.json)."""
+test data file (tests/sauer2014_hetero.json).
+
+The long-double referee of the state functions (gc_derivatives(prec=1), gc_derivatives_vjp_exact) is tied to the same
+fixtures and to the reference's own autograd (tests/golden/deriv_grad.json) before any kernel is judged by it
+(tests/test_gc_state_gpu.py)."""
 import os
 
 import numpy as np
@@ -77,3 +81,80 @@ def test_random_rows(oracle, gg, table, name, dew):
     want_k = np.array(ref["grad_kab"])[ik]
     assert abs(grad[:, 0].sum() - want_k) < 1e-6 * max(1.0, abs(want_k))
     assert np.max(np.abs(grad[:, 3] - np.array(ref["grad_T"])) / np.maximum(1e-12, np.abs(np.array(ref["grad_T"])))) < 1e-8
+
+
+def test_long_double_derivatives_match_reference_python(oracle, gg, table):
+    """prec=1 (long double, safeguarded association) on the reference's 11 pairs, to the tolerances asserted for prec=0."""
+    g = gg["test_inputs"]
+    enc = oracle.gc_encode(table, g["segment_lists"], g["bond_lists"], [tuple(k) for k in g["kab_list"]])
+    a, p, mu, v = oracle.gc_derivatives(enc, g["phi"], g["T"], g["rho"], prec=1)
+    assert np.max(np.abs(a - np.array(g["a"]))) < 1e-14
+    assert np.max(np.abs(p - np.array(g["p"]))) < 1e-14
+    assert np.max(np.abs(mu - np.array(g["mu"]))) < 1e-13
+    assert np.max(np.abs(v / np.array(g["v"]) - 1)) < 1e-12
+    # prec=0 is what it was: the same call without the argument
+    for x, y in zip(oracle.gc_derivatives(enc, g["phi"], g["T"], g["rho"]), oracle.gc_derivatives(enc, g["phi"], g["T"], g["rho"], prec=0)):
+        assert np.array_equal(x, y)
+
+
+VJP_TOL = 1e-7  # of the row's / column's largest component, as tests/test_deriv_grad_gpu.py
+
+
+def _vjp_exact(oracle, table, g):
+    tab = [(s, v) for s, v in table if s in g["table"]]
+    ident = [s for s, _ in tab]
+    enc = oracle.gc_encode(tab, g["segment_lists"], g["bond_lists"], [tuple(k) for k in g["kab_list"]])
+    w = np.array(g["w"])
+    grow, gseg, gkab = oracle.gc_derivatives_vjp_exact(enc, g["phi"], g["T"], g["rho"], w[0], w[1], w[2:4].T, w[4:6].T)
+    leaf = np.array([gkab[ident.index(k[0]), ident.index(k[1])] for k in g["kab_list"]])
+    assert np.array_equal(gkab, gkab.T)
+    return enc, grow, gseg, leaf
+
+
+def _rows_close(got, ref, tol):
+    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
+    got, ref = got.reshape(got.shape[0], -1), ref.reshape(ref.shape[0], -1)
+    err = np.max(np.abs(got - ref), axis=1) / np.maximum(np.max(np.abs(ref), axis=1), 1e-300)
+    assert err.max() < tol, (int(err.argmax()), err.max())
+
+
+def _seg_close(enc, gseg, ref, cols):
+    """[S,8] referee against the reference's [8][S]: per parameter column, over the entries the referee reports (structurally
+    zero parameters and unused segments are 0 in the referee and not compared)."""
+    used = enc["counts"].sum(axis=(0, 1)) > 0
+    for k in cols:
+        mask = used & (enc["seg"][:, k] != 0.0)
+        scale = np.nanmax(np.abs(ref[k]))
+        if not mask.any() or not np.isfinite(scale) or scale == 0.0:
+            continue
+        err = np.max(np.abs(gseg[mask, k] - ref[k][mask])) / scale
+        assert err < VJP_TOL, (k, err)
+        assert np.all(gseg[~mask, k] == 0.0)
+
+
+def test_exact_vjp_matches_reference_autograd_all_classes(oracle, table):
+    """gc_derivatives_vjp_exact against the reference's own autograd: one molecule pair per model class on the table without
+    '>C<', where every gradient of the reference is finite."""
+    g = load_golden("deriv_grad.json")["gc"]["classes"]
+    enc, grow, gseg, leaf = _vjp_exact(oracle, table, g)
+    ref = np.array(g["grad_segments"], dtype=float)
+    assert np.all(np.isfinite(ref))
+    _seg_close(enc, gseg, ref, range(8))
+    assert np.max(np.abs(leaf - np.array(g["grad_kab"]))) < VJP_TOL * np.max(np.abs(g["grad_kab"]))
+    _rows_close(grow[:, 0:2], g["grad_phi"], VJP_TOL)
+    _rows_close(grow[:, 2:3], np.array(g["grad_T"])[:, None], 1e-8)
+    _rows_close(grow[:, 3:5], g["grad_rho"], 1e-8)
+
+
+def test_exact_vjp_matches_reference_autograd_reference_pairs(oracle, table):
+    """The 11 pairs of the reference's test on the full table: its epsilon_k and phi gradients are NaN there ('>C<':
+    sqrt(0) under autograd); everything else must agree, and the referee is finite throughout."""
+    g = load_golden("deriv_grad.json")["gc"]["test_inputs"]
+    enc, grow, gseg, leaf = _vjp_exact(oracle, table, g)
+    ref = np.array(g["grad_segments"], dtype=float)
+    assert np.all(np.isnan(ref[2])) and np.all(np.isnan(np.array(g["grad_phi"], dtype=float)))
+    assert np.all(np.isfinite(gseg)) and np.all(np.isfinite(grow))
+    _seg_close(enc, gseg, ref, [0, 1, 3, 4, 5, 6, 7])
+    assert np.max(np.abs(leaf - np.array(g["grad_kab"]))) < VJP_TOL * np.max(np.abs(g["grad_kab"]))
+    _rows_close(grow[:, 2:3], np.array(g["grad_T"])[:, None], 1e-8)
+    _rows_close(grow[:, 3:5], g["grad_rho"], 1e-8)
