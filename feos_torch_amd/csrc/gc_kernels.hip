@@ -18,16 +18,14 @@ using namespace pcs_abi;
 
 namespace {
 
-constexpr int PCS_GBLOCK = 128;
-constexpr int GBLOCK = PCS_GBLOCK;
+constexpr int GBLOCK = 128;
 // Jacobian kernel: 59 doubles of LDS per thread (bond diameters of the double and the dual model, row bytes); a 256-thread workgroup
 // shares ONE copy of the table among four waves (S = 22: 131 KB, S = 32: 144 KB of the CU's 160 KB) -- 64-thread workgroups fit three
 // times (one wave each): the kernel holds a full register file per wave, so resident waves per CU are what counts
 constexpr int GJBLOCK = 256;
 
-constexpr int PCS_GC_FAST_SS = 6;  // A/B on the synthetic dew batch (scripts/dev/ab_gc.py): 12/12: 9.0 ms, 6/8: 7.9, 4/8: 8.4, 7/7: 8.6
-constexpr int PCS_GC_FAST_NEWTON = 8;
-constexpr int GC_FAST_SS = PCS_GC_FAST_SS, GC_FAST_NEWTON = PCS_GC_FAST_NEWTON;  // fast-pass caps (mix_solver.hpp)
+// fast-pass caps (mix_solver.hpp).  A/B on the synthetic dew batch (scripts/dev/ab_gc.py): 12/12: 9.0 ms, 6/8: 7.9, 4/8: 8.4, 7/7: 8.6
+constexpr int GC_FAST_SS = 6, GC_FAST_NEWTON = 8;
 constexpr int GC_RETRY_BLOCKS = 1024;
 // no-progress leash of the dew-point Newton here (mixture kernels: 20, followed by their damped run): the second pass ends with its
 // slowest row; 10 loses no row of the synthetic batch and shortens it: dew 3.70 -> 3.60 ms per 1e6 rows
@@ -60,21 +58,6 @@ __device__ __forceinline__ int gc_bucket(const unsigned char* __restrict__ row, 
     if (associating == 2 && self_assoc == 1) cls = 2;
     if (associating == 2 && self_assoc == 2) cls = 3;
     return 2 * cls + polar;
-}
-
-template <bool DEW>
-__device__ __forceinline__ void gc_store(int64_t i, int rc, const MixResult& r, double T, double* __restrict__ p_out,
-                                         double* __restrict__ rho4, uint8_t* __restrict__ status,
-                                         int32_t* __restrict__ iters) {
-    const bool ok = rc == BD_OK;
-    if (p_out) p_out[i] = ok ? r.p * T * P_UNIT : 0.0;
-    if (rho4) {
-        double v0 = DEW ? r.spec0 : r.inc0, v1 = DEW ? r.spec1 : r.inc1;
-        double l0 = DEW ? r.inc0 : r.spec0, l1 = DEW ? r.inc1 : r.spec1;
-        reinterpret_cast<double4*>(rho4)[i] = ok ? make_double4(v0, v1, l0, l1) : make_double4(0.0, 0.0, 0.0, 0.0);
-    }
-    if (iters) iters[i] = ok ? r.iters : -1;
-    status[i] = ok ? 0 : 1;
 }
 
 // (A work-queue schedule as in mix_kernels.hip was measured here too: the gc rows need nearly the same number of
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(GBLOCK) void k_gc_bubble_dew(const double* __restri
             const int slot = atomicAdd(&retry[0], 1);
             if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)i;  // bounded append (see pure_kernels.hip)
         } else {
-            gc_store<DEW>(i, rc, r, T, p_out, rho4, status, iters);
+            store_bubble_dew<DEW>(i, rc, r, T, p_out, rho4, status, iters);
         }
         if (!RETRY) break;
     }
@@ -314,6 +297,18 @@ __global__ __launch_bounds__(GJBLOCK) void k_gc_jacobian(int dew, const double* 
     }
 }
 
+// fast pass over all rows and, with a work list, the robust pass over the rows it gave up on
+template <bool DEW>
+void launch_gc_bubble_dew(unsigned grid, size_t lds, hipStream_t s, const double* table, int S, const uint8_t* rows, const double* phi,
+                          const double* temp, const double* z, const double* p_init, int64_t n, double* p_out, double* rho4,
+                          uint8_t* status, int32_t* iters, int32_t* retry, const int32_t* order) {
+    hipLaunchKernelGGL((k_gc_bubble_dew<DEW, false>), dim3(grid), dim3(GBLOCK), lds, s, table, S, rows, phi, temp, z, p_init, n, p_out,
+                       rho4, status, iters, retry, order);
+    if (retry)
+        hipLaunchKernelGGL((k_gc_bubble_dew<DEW, true>), dim3(GC_RETRY_BLOCKS), dim3(GBLOCK), lds, s, table, S, rows, phi, temp, z,
+                           p_init, n, p_out, rho4, status, iters, retry, order);
+}
+
 }  // namespace
 
 extern "C" {
@@ -335,19 +330,8 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
     if (retry) {
         if (int e = zero_ints(retry, 1, s)) return e;
     }
-    if (dew) {
-        hipLaunchKernelGGL((k_gc_bubble_dew<true, false>), dim3(grid), dim3(GBLOCK), lds, s, table, S, rows, phi, temp, z, p_init,
-                           n, p_out, rho4, status, iters, retry, order);
-        if (retry)
-            hipLaunchKernelGGL((k_gc_bubble_dew<true, true>), dim3(GC_RETRY_BLOCKS), dim3(GBLOCK), lds, s, table, S, rows, phi,
-                               temp, z, p_init, n, p_out, rho4, status, iters, retry, order);
-    } else {
-        hipLaunchKernelGGL((k_gc_bubble_dew<false, false>), dim3(grid), dim3(GBLOCK), lds, s, table, S, rows, phi, temp, z,
-                           p_init, n, p_out, rho4, status, iters, retry, order);
-        if (retry)
-            hipLaunchKernelGGL((k_gc_bubble_dew<false, true>), dim3(GC_RETRY_BLOCKS), dim3(GBLOCK), lds, s, table, S, rows, phi,
-                               temp, z, p_init, n, p_out, rho4, status, iters, retry, order);
-    }
+    (dew ? launch_gc_bubble_dew<true> : launch_gc_bubble_dew<false>)(grid, lds, s, table, S, rows, phi, temp, z, p_init, n, p_out, rho4, status,
+                                                                     iters, retry, order);
     return launched("k_gc_bubble_dew launch");
 }
 

@@ -6,12 +6,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <cstddef>
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
 #include "block_order.hpp"
 #include "mix_model.hpp"
-#include <cstddef>
 #include "mix_solver.hpp"
 #include "mix_solver_sm.hpp"
 #include "mix_jacobian.hpp"
@@ -26,24 +26,7 @@ constexpr int MBLOCK = 128;
 
 // lanes that must be idle before a queue wave refills: the refill code (row load, coefficient set-up) runs for the whole
 // wave (A/B dew 1e6 rows, round 1, one kernel: 1: 7.9 ms, 4: 7.7, 8: 7.5, 16: 7.8; round 3, two kernels: 8: 4.93, 12: 4.84, 16: 4.83, 24: 4.89)
-constexpr int PCS_REFILL_MIN = 16;
-constexpr int REFILL_MIN = PCS_REFILL_MIN;
-
-template <bool DEW>
-__device__ __forceinline__ void mix_store(int64_t i, int rc, const MixResult& r, double T, double* __restrict__ p_out,
-                                          double* __restrict__ rho4, uint8_t* __restrict__ status,
-                                          int32_t* __restrict__ iters) {
-    const bool ok = rc == BD_OK;
-    if (p_out) p_out[i] = ok ? r.p * T * P_UNIT : 0.0;
-    if (rho4) {
-        // reference layout (src/pcsaft.rs:225-228): [rhoV_1, rhoV_2, rhoL_1, rhoL_2]
-        double v0 = DEW ? r.spec0 : r.inc0, v1 = DEW ? r.spec1 : r.inc1;
-        double l0 = DEW ? r.inc0 : r.spec0, l1 = DEW ? r.inc1 : r.spec1;
-        reinterpret_cast<double4*>(rho4)[i] = ok ? make_double4(v0, v1, l0, l1) : make_double4(0.0, 0.0, 0.0, 0.0);
-    }
-    if (iters) iters[i] = ok ? r.iters : -1;
-    status[i] = ok ? 0 : 1;
-}
+constexpr int REFILL_MIN = 16;
 
 // K5 without a workspace: one row per lane in a single pass with the full iteration caps, the robust second attempt in
 // place.  Same arithmetic as the work-queue schedule below (tests/test_mix_missed_gpu.py), several times slower: a wave
@@ -77,7 +60,7 @@ __global__ __launch_bounds__(MBLOCK, 1) void k_mix_bubble_dew(const double* __re
     bool root_failed = false;
     int rc = bubble_dew_solve_sm<DEW>(m, z[i], p_red, r, SS_MAX_IT, NEWTON_MAX_IT, false, &root_failed);
     if (rc != BD_OK && root_failed) rc = bubble_dew_solve_sm<DEW>(m, z[i], p_red, r, SS_MAX_IT, NEWTON_MAX_IT, true);
-    mix_store<DEW>(i, rc, r, T, p_out, rho4, status, iters);
+    store_bubble_dew<DEW>(i, rc, r, T, p_out, rho4, status, iters);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -424,7 +407,7 @@ __global__ __launch_bounds__(64, 1) void k_mix_bubble_dew_queue(const double* __
                 if (code == INIT_FAILED) {
                     const int64_t row = perm[pos];
                     L.idle();  // rc = BD_FAILED, final
-                    mix_store<DEW>(row, BD_FAILED, L.out, temp[row], p_out, rho4, status, iters);
+                    store_bubble_dew<DEW>(row, BD_FAILED, L.out, temp[row], p_out, rho4, status, iters);
                 } else if (code >= 0) {
                     r = take_row(params, kij, temp, z, p_init, perm[pos], m);
                     if (code == INIT_ROBUST) {
@@ -483,7 +466,7 @@ __global__ __launch_bounds__(64, 1) void k_mix_bubble_dew_queue(const double* __
                 L.start(m, r.z, r.p_red, SS_MAX_IT, NEWTON_MAX_IT, true);
                 evals = 0;
             }
-            if (L.done()) mix_store<DEW>(r.row, L.rc, L.out, r.T, p_out, rho4, status, iters);
+            if (L.done()) store_bubble_dew<DEW>(r.row, L.rc, L.out, r.T, p_out, rho4, status, iters);
         }
     }
 }
@@ -595,6 +578,37 @@ int launch_mix_class_order(const double* params, int64_t n, void* workspace, hip
     return 0;
 }
 
+// work-queue schedule: perm[n] + control block, pre-pass fugacities, init records and the robust list in the workspace
+template <bool DEW>
+int launch_mix_queue(const double* params, const double* kij, const double* temp, const double* z, const double* p_init, int64_t n,
+                     double* p_out, double* rho4, uint8_t* status, int32_t* iters, void* workspace, hipStream_t s) {
+    int32_t* perm = static_cast<int32_t*>(workspace);
+    int32_t* ctrl = perm + n;
+    double* fug = reinterpret_cast<double*>(static_cast<char*>(workspace) + mix_ws_offset(n));
+    double4* init = reinterpret_cast<double4*>(fug + 4 * n);
+    int32_t* robust_list = reinterpret_cast<int32_t*>(fug + 8 * n);
+    if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
+    if (DEW)
+        hipLaunchKernelGGL(k_mix_pure_fugacity, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, s, params, temp, n,
+                           (const int32_t*)perm, fug);
+    unsigned waves = (unsigned)queue_waves();
+    const unsigned needed = grid_for(n, 64);
+    if (waves > needed) waves = needed;
+    hipLaunchKernelGGL(k_mix_init_queue<DEW>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n, (const int32_t*)perm, ctrl,
+                       DEW ? (const double*)fug : (const double*)nullptr, init, robust_list);
+    hipLaunchKernelGGL(k_mix_bubble_dew_queue<DEW>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n, (const int32_t*)perm,
+                       ctrl, (const double4*)init, (const int32_t*)robust_list, p_out, rho4, status, iters);
+    return launched("k_mix_bubble_dew_queue launch");
+}
+
+template <bool DEW>
+int launch_mix_single(const double* params, const double* kij, const double* temp, const double* z, const double* p_init, int64_t n,
+                      double* p_out, double* rho4, uint8_t* status, int32_t* iters, hipStream_t s) {
+    hipLaunchKernelGGL(k_mix_bubble_dew<DEW>, dim3(grid_for(n, MBLOCK)), dim3(MBLOCK), 0, s, params, kij, temp, z, p_init, n, p_out,
+                       rho4, status, iters);
+    return launched("k_mix_bubble_dew launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -612,43 +626,9 @@ int pcs_mix_bubble_dew(int dew, const double* params, const double* kij, const d
                        void* workspace, void* stream) {
     if (int e = enter(n, params && kij && temp && z && p_init && status, "pcs_mix_bubble_dew: null required pointer"); e != GO_ON) return e;
     hipStream_t s = as_stream(stream);
-    if (workspace) {
-        // work-queue schedule: perm[n] + control block, pre-pass fugacities, init records and the robust list in the workspace
-        int32_t* perm = static_cast<int32_t*>(workspace);
-        int32_t* ctrl = perm + n;
-        double* fug = reinterpret_cast<double*>(static_cast<char*>(workspace) + mix_ws_offset(n));
-        double4* init = reinterpret_cast<double4*>(fug + 4 * n);
-        int32_t* robust_list = reinterpret_cast<int32_t*>(fug + 8 * n);
-        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
-        if (dew)
-            hipLaunchKernelGGL(k_mix_pure_fugacity, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, s, params, temp, n,
-                               (const int32_t*)perm, fug);
-        unsigned waves = (unsigned)queue_waves();
-        const unsigned needed = grid_for(n, 64);
-        if (waves > needed) waves = needed;
-        if (dew) {
-            hipLaunchKernelGGL(k_mix_init_queue<true>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n,
-                               (const int32_t*)perm, ctrl, (const double*)fug, init, robust_list);
-            hipLaunchKernelGGL(k_mix_bubble_dew_queue<true>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n,
-                               (const int32_t*)perm, ctrl, (const double4*)init, (const int32_t*)robust_list, p_out, rho4, status,
-                               iters);
-        } else {
-            hipLaunchKernelGGL(k_mix_init_queue<false>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n,
-                               (const int32_t*)perm, ctrl, (const double*)nullptr, init, robust_list);
-            hipLaunchKernelGGL(k_mix_bubble_dew_queue<false>, dim3(waves), dim3(64), 0, s, params, kij, temp, z, p_init, n,
-                               (const int32_t*)perm, ctrl, (const double4*)init, (const int32_t*)robust_list, p_out, rho4, status,
-                               iters);
-        }
-        return launched("k_mix_bubble_dew_queue launch");
-    }
-    const unsigned grid = grid_for(n, MBLOCK);
-    if (dew)
-        hipLaunchKernelGGL(k_mix_bubble_dew<true>, dim3(grid), dim3(MBLOCK), 0, s, params, kij, temp, z, p_init, n, p_out, rho4,
-                           status, iters);
-    else
-        hipLaunchKernelGGL(k_mix_bubble_dew<false>, dim3(grid), dim3(MBLOCK), 0, s, params, kij, temp, z, p_init, n, p_out, rho4,
-                           status, iters);
-    return launched("k_mix_bubble_dew launch");
+    if (workspace)
+        return (dew ? launch_mix_queue<true> : launch_mix_queue<false>)(params, kij, temp, z, p_init, n, p_out, rho4, status, iters, workspace, s);
+    return (dew ? launch_mix_single<true> : launch_mix_single<false>)(params, kij, temp, z, p_init, n, p_out, rho4, status, iters, s);
 }
 
 int pcs_mix_derivatives(const double* params, const double* kij, const double* temp, const double* rho, int64_t n,

@@ -12,14 +12,16 @@
 // of the model is not finite), refined by ideal-vapour successive substitution: a scalar fixed-point
 // map in ln(x_1/x_2), iterated with secant steps, the liquid density carried along by the Newton step
 // each sweep's evaluation provides (re-solved, from the tracked density, only when that step is large).
-// This file holds the evaluation entry point, the constants and the pieces shared by every driver; the iteration itself
-// is the per-lane state machine of mix_solver_sm.hpp (restated sequentially by the CPU oracle, oracle/mix_solver.hpp).
+// This file holds the evaluation entry point, the constants and the pieces shared by every driver (3x3 solve, result store); the
+// iteration itself is the per-lane state machine of mix_solver_sm.hpp (restated sequentially by the CPU oracle, oracle/mix_solver.hpp).
 // The returned pressure is the reference's final explicit Newton step (feos_torch/
 // pcsaft_mix.py:435-444 / :459-468) evaluated at the converged densities.
 //
 // `Model` = a coefficient struct with  template<class R> R a(const R& r0, const R& r1) const  and
 // packing(x0, x1) = zeta3 / rho_total.  Shared by PcSaftMix and GcPcSaftMix kernels.
 #pragma once
+#include <stdint.h>
+
 #include "dual.hpp"
 #include "pcsaft_consts.hpp"
 
@@ -42,9 +44,7 @@ struct PhaseEval {
 // caller's stack frame by ~37 loads per evaluation (512 -> 104-160 B of scratch): bubble 2.34 -> 2.20 ms, dew 4.94 -> 4.61 ms
 // per 1e6 rows, results within 5e-13.  (The gc solver kernel, whose state machine is instantiated for two attempts and keeps its
 // state in registers, gets slower inlined: dew 3.66 -> 4.2 ms.)
-#ifndef PCS_EVAL_ATTR
 #define PCS_EVAL_ATTR __device__ __attribute__((noinline))
-#endif
 // Value, gradient and Hessian of a in the partial densities.  Evaluated in the coordinates (u, w) = (zeta_3, rho_2) -- the
 // packing fraction zeta_3 = c0 rho_1 + c1 rho_2 (c_i = packing(e_i) > 0) is a linear, invertible change of the first
 // coordinate -- so that every function of the packing fraction alone is a one-variable Taylor series (dual.hpp, "D2 (x)
@@ -167,6 +167,22 @@ PCS_DEV double bubble_dew_formula(const PhaseEval& s, const PhaseEval& n) {
 
 // Return codes of bubble_dew_solve
 enum : int { BD_OK = 0, BD_FAILED = 1, BD_CAP = 2 };
+
+// one row of a bubble / dew kernel; a row that is not BD_OK stores zeros, iters = -1 and status 1
+template <bool DEW>
+PCS_DEV void store_bubble_dew(int64_t i, int rc, const MixResult& r, double T, double* __restrict__ p_out, double* __restrict__ rho4,
+                              uint8_t* __restrict__ status, int32_t* __restrict__ iters) {
+    const bool ok = rc == BD_OK;
+    if (p_out) p_out[i] = ok ? r.p * T * P_UNIT : 0.0;
+    if (rho4) {
+        // reference layout (src/pcsaft.rs:225-228): [rhoV_1, rhoV_2, rhoL_1, rhoL_2]
+        double v0 = DEW ? r.spec0 : r.inc0, v1 = DEW ? r.spec1 : r.inc1;
+        double l0 = DEW ? r.inc0 : r.spec0, l1 = DEW ? r.inc1 : r.spec1;
+        reinterpret_cast<double4*>(rho4)[i] = ok ? make_double4(v0, v1, l0, l1) : make_double4(0.0, 0.0, 0.0, 0.0);
+    }
+    if (iters) iters[i] = ok ? r.iters : -1;
+    status[i] = ok ? 0 : 1;
+}
 
 // (The sequential, readable form of the solver -- nested loops instead of a state machine -- is the CPU oracle's
 // oracle/mix_solver.hpp, which restates mix_solver_sm.hpp decision by decision; the device-side copy of it that rounds 1-2

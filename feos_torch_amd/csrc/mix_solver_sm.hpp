@@ -17,15 +17,12 @@
 #pragma once
 #include "mix_solver.hpp"
 
-
 namespace pcs {
 
 // evaluations a robust second attempt may use (all drivers).  Rows it recovers need a bracketed root (~8) + a few Newton
 // iterations (bubble) resp. two pure roots + ~5 sweeps + ~8 Newton iterations (dew); rows without a solution would run
 // 200-350 evaluations each and, being few and scattered, make up the tail of the work-queue kernel
-constexpr int PCS_ROBUST_BUDGET_BUBBLE = 48;
-constexpr int PCS_ROBUST_BUDGET_DEW = 96;
-template <bool DEW> constexpr int robust_eval_budget() { return DEW ? PCS_ROBUST_BUDGET_DEW : PCS_ROBUST_BUDGET_BUBBLE; }
+template <bool DEW> constexpr int robust_eval_budget() { return DEW ? 96 : 48; }
 
 // Per-lane solver state.  start() -> { point(); e = phase_eval(...); consume(e); } until done().
 // `robust` (second attempt on a row the plain form gives up on; a run-time flag of the lane so that a persistent wave can
@@ -211,8 +208,6 @@ struct BdLane {
 
     template <class Model>
     PCS_DEV void consume(const Model& m, const PhaseEval& e) {
-#define PCS_SM_START_ROOT(who, xa, xb, pspec, has_alt, palt) start_root(m, who, xa, xb, pspec, has_alt, palt)
-#define PCS_SM_START_ROOT_WARM(who, xa, xb, pspec, has_alt, palt, rho0) start_root(m, who, xa, xb, pspec, has_alt, palt, rho0)
         if (stage == S_ROOT) {
             double p = e.p(), dp = r_x0 * e.dp0() + r_x1 * e.dp1();
             bool bad = false, done = false;
@@ -249,37 +244,39 @@ struct BdLane {
                     if (!done && r_it >= 2 * LIQ_ROOT_MAX_IT) bad = true;
                 }
             } else {
-            if (r_it == 0 && !r_dense && !r_warm && !(p > r_pspec)) {
-                r_rho = 0.62 / r_pk;  // very cold / dense: restart on the dense side (plain Newton from there)
-                r_dense = true;
-                return;
-            }
-            double den = r_dense ? dp : dp - 4.0 * (p - r_pspec) * r_pk * d_recip(1.0 - r_rho * r_pk);
-            bad = !(dp > 0.0) || !(den > 0.0) || !is_finite_bits(p);
-            step = (p - r_pspec) * d_recip(den);
-            rho_new = r_rho - step;
-            bad = bad || !(rho_new > 0.0) || !is_finite_bits(rho_new);
-            // dense restart: the root is bracketed by eta = 0.5 (p < p_spec) and 0.62 (p > p_spec).  An iterate that leaves
-            // that interval is on its way to ANOTHER liquid-like root of a very cold fluid (the pressure is not monotone up
-            // there); which one the plain Newton would land on is a matter of luck, so the row goes to the robust form, whose
-            // systematic search always takes the first bracket above eta = 0.5
-            bad = bad || (r_dense && !(rho_new * r_pk > 0.5 && rho_new * r_pk < 0.62));
-            if (!bad) {
-                double err = fabs(step) * d_recip(r_rho);
-                done = err <= LIQ_ROOT_TOL || (r_it >= 3 && err < 1e-7 && err >= 0.25 * r_errprev);
-                r_errprev = err;
-                r_it++;
-                if (!done && r_it >= LIQ_ROOT_MAX_IT) bad = true;
-            }
+                // plain form.  Restated for a whole wave at p_spec = 0 by pure_fugacities_on_the_line (below) and k_mix_pure_fugacity
+                // (mix_kernels.hip) -- same start, scaled function, dense restart, acceptance rule: the three must change together
+                if (r_it == 0 && !r_dense && !r_warm && !(p > r_pspec)) {
+                    r_rho = 0.62 / r_pk;  // very cold / dense: restart on the dense side (plain Newton from there)
+                    r_dense = true;
+                    return;
+                }
+                double den = r_dense ? dp : dp - 4.0 * (p - r_pspec) * r_pk * d_recip(1.0 - r_rho * r_pk);
+                bad = !(dp > 0.0) || !(den > 0.0) || !is_finite_bits(p);
+                step = (p - r_pspec) * d_recip(den);
+                rho_new = r_rho - step;
+                bad = bad || !(rho_new > 0.0) || !is_finite_bits(rho_new);
+                // dense restart: the root is bracketed by eta = 0.5 (p < p_spec) and 0.62 (p > p_spec).  An iterate that leaves
+                // that interval is on its way to ANOTHER liquid-like root of a very cold fluid (the pressure is not monotone up
+                // there); which one the plain Newton would land on is a matter of luck, so the row goes to the robust form, whose
+                // systematic search always takes the first bracket above eta = 0.5
+                bad = bad || (r_dense && !(rho_new * r_pk > 0.5 && rho_new * r_pk < 0.62));
+                if (!bad) {
+                    double err = fabs(step) * d_recip(r_rho);
+                    done = err <= LIQ_ROOT_TOL || (r_it >= 3 && err < 1e-7 && err >= 0.25 * r_errprev);
+                    r_errprev = err;
+                    r_it++;
+                    if (!done && r_it >= LIQ_ROOT_MAX_IT) bad = true;
+                }
             }
             if (bad && r_warm) {  // the warm start left the liquid branch: same root from the cold start
-                PCS_SM_START_ROOT(r_for, r_x0, r_x1, r_pspec, r_has_alt, r_palt);
+                start_root(m, r_for, r_x0, r_x1, r_pspec, r_has_alt, r_palt);
                 return;
             }
             if (bad) {
                 root_failed = true;
                 if (r_has_alt) {  // second choice of the specified pressure
-                    PCS_SM_START_ROOT(r_for, r_x0, r_x1, r_palt, false, 0.0);
+                    start_root(m, r_for, r_x0, r_x1, r_palt, false, 0.0);
                 } else if (!robust && (r_for == R_PURE0 || r_for == R_PURE1)) {
                     // plain form: a pure-liquid root that the plain Newton cannot find (very cold component) -- give the row
                     // to the robust form at once instead of iterating from an uninformed start
@@ -287,7 +284,7 @@ struct BdLane {
                 } else if (r_for == R_PURE0 || r_for == R_PURE1) {
                     // no Raoult estimate: start the substitution from the vapour composition at the caller's pressure
                     p0 = p_init; x0 = z0; x1 = z1;
-                    PCS_SM_START_ROOT(R_SS, x0, x1, 0.0, true, p0);
+                    start_root(m, R_SS, x0, x1, 0.0, true, p0);
                 } else {
                     stage = S_DONE;  // rc = BD_FAILED
                 }
@@ -300,7 +297,7 @@ struct BdLane {
             if (r_for == R_PURE0) {
                 f0 = rho_new * exp(g0c);
                 rl0 = rho_new;
-                PCS_SM_START_ROOT(R_PURE1, 0.0, 1.0, 0.0, false, 0.0);
+                start_root(m, R_PURE1, 0.0, 1.0, 0.0, false, 0.0);
                 return;
             }
             if (r_for == R_PURE1) {
@@ -331,7 +328,7 @@ struct BdLane {
             if (!(fine && fabs(drho) <= 0.05 * rl)) {
                 if (!resolved) {  // composition moved a lot: re-solve the liquid root here, then redo the sweep
                     resolved = true;
-                    PCS_SM_START_ROOT_WARM(R_SS, x0, x1, 0.0, true, p0, fine ? rl : 0.0);
+                    start_root(m, R_SS, x0, x1, 0.0, true, p0, fine ? rl : 0.0);
                     return;
                 }
                 if (!fine) { stage = S_DONE; return; }
@@ -485,9 +482,6 @@ struct BdLane {
             }
             return;
         }
-
-#undef PCS_SM_START_ROOT
-#undef PCS_SM_START_ROOT_WARM
     }
 };
 

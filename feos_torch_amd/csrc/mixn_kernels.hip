@@ -11,6 +11,7 @@
 // from which (pcsaft_mix.py:395-420)  p = sum rho - a + e2,  mu_i = e1[i],  v_i = (1 + e12[i]) / (sum rho + e12[nc]).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
@@ -342,6 +343,19 @@ __global__ __launch_bounds__(NBLOCK) void k_mixn_derivatives_vjp(const double* _
     }
 }
 
+// f(std::integral_constant<int, NC>{}) for the run-time number of components (checked by the callers: 1 .. 6)
+template <class F>
+void with_ncomp(int ncomp, F f) {
+    switch (ncomp) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        default: f(std::integral_constant<int, 6>{}); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -355,14 +369,7 @@ int pcs_mixn_derivatives(const double* params, const double* temp, const double*
     if (!params || !temp || !rho) return fail_msg("pcs_mixn_derivatives: null required pointer");
     const dim3 grid(grid_for(n, NBLOCK)), block(NBLOCK);
     hipStream_t s = as_stream(stream);
-    switch (ncomp) {
-        case 1: hipLaunchKernelGGL(k_mixn_derivatives<1>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-        case 2: hipLaunchKernelGGL(k_mixn_derivatives<2>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-        case 3: hipLaunchKernelGGL(k_mixn_derivatives<3>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-        case 4: hipLaunchKernelGGL(k_mixn_derivatives<4>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-        case 5: hipLaunchKernelGGL(k_mixn_derivatives<5>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-        default: hipLaunchKernelGGL(k_mixn_derivatives<6>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); break;
-    }
+    with_ncomp(ncomp, [&](auto nc) { hipLaunchKernelGGL(k_mixn_derivatives<nc()>, grid, block, 0, s, params, temp, rho, n, a, p, mu, v); });
     return launched("k_mixn_derivatives launch");
 }
 
@@ -375,14 +382,9 @@ int pcs_mixn_derivatives_vjp(const double* params, const double* temp, const dou
     if (!params || !temp || !rho || !grad) return fail_msg("pcs_mixn_derivatives_vjp: null required pointer");
     const dim3 grid(grid_for(n, NBLOCK)), block(NBLOCK);
     hipStream_t s = as_stream(stream);
-    switch (ncomp) {
-        case 1: hipLaunchKernelGGL(k_mixn_derivatives_vjp<1>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-        case 2: hipLaunchKernelGGL(k_mixn_derivatives_vjp<2>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-        case 3: hipLaunchKernelGGL(k_mixn_derivatives_vjp<3>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-        case 4: hipLaunchKernelGGL(k_mixn_derivatives_vjp<4>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-        case 5: hipLaunchKernelGGL(k_mixn_derivatives_vjp<5>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-        default: hipLaunchKernelGGL(k_mixn_derivatives_vjp<6>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad); break;
-    }
+    with_ncomp(ncomp, [&](auto nc) {
+        hipLaunchKernelGGL(k_mixn_derivatives_vjp<nc()>, grid, block, 0, s, params, temp, rho, n, g_a, g_p, g_mu, g_v, grad);
+    });
     return launched("k_mixn_derivatives_vjp launch");
 }
 

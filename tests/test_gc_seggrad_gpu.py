@@ -170,3 +170,48 @@ def test_gradient_accumulates_and_validates(amd, table):
     assert float(((g3 - 2.0 * g1).abs() / scale).max()) < 1e-12
     with pytest.raises(ValueError):
         native.gc_segment_gradient(tab, eos.S, rows, ph[:-1], Tk, rho4, False)
+
+
+@pytest.fixture(scope="module")
+def converged(amd, table):
+    """{dew: (table, S, rows, phi, T, rho4)}: the first 512 rows of gc_batch(640, seed=12) that the kernels' own solver converges."""
+    from feos_torch_amd import native
+    from feos_torch_amd.synthetic import gc_batch
+
+    b = gc_batch(640, table, seed=12)
+    eos = amd.GcPcSaftMix([s for s, _ in table], tuple(torch.tensor([v[k] for _, v in table], dtype=f64) for k in range(8)),
+                          b["segment_lists"], b["bond_lists"], b["kab_list"], torch.tensor(b["phi"], dtype=f64))
+    dev = eos.rows.device
+    d = lambda x: torch.tensor(x, dtype=f64, device=dev)
+    tab, phi, T = eos._table(), d(b["phi"]), d(b["T"])
+    out = {}
+    for dew in (False, True):
+        r = native.gc_bubble_dew(tab, eos.S, eos.rows, phi, T, d(b["x"]), d(b["p_init"]), dew)
+        ok = torch.nonzero(~r["status"].bool()).flatten()[:512]
+        assert ok.numel() == 512
+        out[dew] = (tab, eos.S, eos.rows[ok].contiguous(), phi[ok].contiguous(), T[ok].contiguous(), r["rho4"][ok].contiguous())
+    return out
+
+
+@pytest.mark.parametrize("dew", [False, True])
+def test_jacobian_and_segment_gradient_ragged_sizes_are_consistent(converged, dew):
+    """pcs_gc_jacobian and pcs_gc_segment_gradient (bubble / dew mode) on n = 1, 255, 256, 257 rows (256 = the Jacobian kernel's
+    workgroup, 257 the first size with a one-lane workgroup): jac and agg have the bits of the first n rows of one 512-row call;
+    the segment gradient, a sum over the batch, is additive over the split, grad(rows[:n]) + grad(rows[n:512]) = grad(rows[:512]),
+    to 1e-12 of each column's largest entry (tests/test_gc_state_gpu.py: only the order of the atomic additions differs)."""
+    from feos_torch_amd import native
+
+    tab, S, rows, phi, T, rho4 = converged[dew]
+    bits = lambda x: x.contiguous().view(torch.int64)
+    jac, agg = native.gc_jacobian(tab, S, rows, phi, T, rho4, dew)
+    whole = native.gc_segment_gradient(tab, S, rows, phi, T, rho4, dew)
+    assert bool(torch.isfinite(jac).all()) and bool(torch.isfinite(agg).all()) and bool(torch.isfinite(whole).all())
+    scale = whole.abs().max(dim=0).values.clamp_min(1e-300)
+    for n in (1, 255, 256, 257):
+        jn, an = native.gc_jacobian(tab, S, rows[:n], phi[:n], T[:n], rho4[:n], dew)
+        assert jn.shape == (n, 7) and torch.equal(bits(jn), bits(jac[:n])), n
+        assert an.shape == (n, 6) and torch.equal(bits(an), bits(agg[:n])), n
+        head = native.gc_segment_gradient(tab, S, rows[:n], phi[:n], T[:n], rho4[:n], dew)
+        tail = native.gc_segment_gradient(tab, S, rows[n:], phi[n:], T[n:], rho4[n:], dew)
+        err = float(((head + tail - whole).abs() / scale).max())
+        assert err < 1e-12, (n, err)
