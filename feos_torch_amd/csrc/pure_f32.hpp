@@ -17,7 +17,7 @@ constexpr float PCS_F32_TAYLOR_MAX = 1e-3f;
 constexpr float PCS_F32_PREDICT_TOL_L = 5e-6f;
 constexpr float PCS_F32_PREDICT_TOL_V = 5e-5f;
 constexpr float PCS_F32_PREDICT_CMAX = 1e3f;
-constexpr int PCS_F32_DENSE_LEVELS = 3;  // restarts of the fp32 liquid root on the dense side (1 = eta 0.58 only)
+constexpr int PCS_F32_DENSE_LEVELS = 3;  // rungs of the fp32 liquid root's dense-side ladder (1 = eta 0.58 only)
 // Lean coupled iterations (a and a' only; dp/drho carried and updated from the pressures in hand: carry_slope,
 // presolve_coupled):
 // LEAN_MAX:   largest relative vapour step after which the next vapour evaluation may be lean: every ordinary step (a step
@@ -517,11 +517,24 @@ struct LiquidRootF {
 template <bool AT_START>
 PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float tol_dense, int it, const EvalF& e, LiquidRootF& s) {
     const float res = e.p - p_spec;
-    if (it == s.first && it < PCS_F32_DENSE_LEVELS && finitef(e.p) && !(res > 0.0f)) {
-        // still on the dilute side of the root: next start 0.08 further up (eta = 0.58, 0.66, 0.74)
+    // rung of the ladder eta = 0.58, 0.66, 0.74 above this start (a start within 0.005 below a rung takes the one after it, so
+    // every restart moves up; PCS_F32_DENSE_LEVELS: none left)
+    const float eta = AT_START ? PCS_F32_START_ETA : s.rl * f.ceta;
+    const int rung = AT_START ? 0 : eta < 0.575f ? 0 : eta < 0.655f ? 1 : eta < 0.735f ? 2 : PCS_F32_DENSE_LEVELS;
+    if (it == s.first && rung < PCS_F32_DENSE_LEVELS && finitef(e.p) && !(res > 0.0f)) {
+        // still on the dilute side of the root: the next start lies on its dense side
         s.dense = true;
         s.first = it + 1;
-        s.rl = (0.58f + 0.08f * (float)it) / f.ceta;
+        float rn = (0.58f + 0.08f * (float)rung) / f.ceta;
+        if (AT_START && e.dp > 0.0f) {
+            // on the liquid branch below the root, p convex from here on (hard-sphere pole): the plain Newton point lies above
+            // the root and costs no evaluation; the ladder stays behind it (an evaluation there that is still not above the
+            // root -- second loop of strongly polar sets -- goes on to the rung above it)
+            const float r1 = s.rl - res * __builtin_amdgcn_rcpf(e.dp);
+            const float eta1 = r1 * f.ceta;
+            if (finitef(r1) && eta1 > PCS_F32_START_ETA && eta1 <= 0.74f) rn = r1;
+        }
+        s.rl = rn;
     } else if (!finitef(e.p) || !(e.dp > 0.0f) || (it == s.first && !(res > 0.0f))) {
         s.ok = false;
         s.done = true;
@@ -538,8 +551,10 @@ PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float
 // fp32 liquid root of p(rho) = p_spec from eta = 0.5.  Newton on (p - p_spec)(1-eta)^4 = 0 (same root):
 // the hard-sphere pole makes p(rho) very steep on the dense side, the scaled function is close to
 // linear -> 2-3 evaluations instead of 4-6 to a 10 % step.  Strongly attractive rows (large dipole /
-// association at low T) have their liquid above eta = 0.5: they restart at eta = 0.58 on its dense side
-// with plain Newton (monotone from there) and the tighter `tol_dense`.
+// association at low T) have their liquid above eta = 0.5: they restart on its dense side, at the plain Newton point
+// from eta = 0.5 (p is convex there, so the point lies above the root; no evaluation spent on finding one) or, where
+// that point is unusable or still below the root, on the ladder eta = 0.58, 0.66, 0.74, and go on with plain Newton
+// (monotone from there) and the tighter `tol_dense`.
 // Wave-uniform loop; returns false when the lane must use the fp64 initialiser.  Iteration 0 is peeled: every lane is at
 // eta0 there and takes pure_eval_start_f32.
 PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float tol_dense, int cap, float& rl,
