@@ -6,6 +6,11 @@
 
 #include "mix_model.hpp"
 
+namespace pcs_abi {
+// batch-wide class order of the rows (mix_kernels.hip): perm[n] + control block in a workspace of pcs_workspace_bytes(n)
+int launch_mix_class_order(const double* params, int64_t n, void* workspace, hipStream_t s);
+}  // namespace pcs_abi
+
 namespace {
 
 using namespace pcs;

@@ -565,9 +565,12 @@ int queue_waves() {
     return waves;
 }
 
+}  // namespace
+
 // Batch-wide class order: zeroes the control block behind perm[n] in the workspace and fills perm (expensive classes first).
-// The launches are checked by the caller's launched() at the end of its own sequence.
-int launch_mix_class_order(const double* params, int64_t n, void* workspace, hipStream_t s) {
+// The launches are checked by the caller's launched() at the end of its own sequence.  External linkage (declared in
+// mix_kernel_common.hpp): mix_temperature.hip orders its rows with it too.
+int pcs_abi::launch_mix_class_order(const double* params, int64_t n, void* workspace, hipStream_t s) {
     int32_t* perm = static_cast<int32_t*>(workspace);
     int32_t* ctrl = perm + n;
     if (int ez = zero_ints(ctrl, QCTRL_INTS, s)) return ez;
@@ -577,6 +580,8 @@ int launch_mix_class_order(const double* params, int64_t n, void* workspace, hip
     hipLaunchKernelGGL(k_mix_class_scatter, dim3(g256), dim3(256), 0, s, params, n, ctrl, perm);
     return 0;
 }
+
+namespace {
 
 // work-queue schedule: perm[n] + control block, pre-pass fugacities, init records and the robust list in the workspace
 template <bool DEW>

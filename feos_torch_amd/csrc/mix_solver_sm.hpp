@@ -601,4 +601,47 @@ PCS_DEV int bubble_dew_solve_sm_both(const Model& m, double z0, double p_init, M
     return L.done() ? L.rc : BD_FAILED;
 }
 
+// One trial of an outer iteration that solves for the temperature (mix_temperature.hpp): the bubble / dew solve at the
+// model's temperature on the lanes with `on` (wave-uniform call; the others idle).  warm: the Newton stage from
+// (rho_spec, rho_inc_1, rho_inc_2) of a neighbouring temperature, without the damped second run; where it does not end in
+// BD_OK -- and on every lane without a warm start -- the cold solve as the single-pass kernel runs it: the plain form, then,
+// only if one of its liquid roots failed, the robust form.  One loop and one evaluation site for all three, restarted in
+// place like bubble_dew_solve_sm_both; the arithmetic of each attempt is the state machine's.
+template <bool DEW, class Model>
+PCS_DEV int bubble_dew_trial_sm(const Model& m, double z0, double p_init, bool on, bool warm, double rs, double ri0, double ri1,
+                                MixResult& out) {
+    BdLane<DEW> L;
+    L.idle();
+    bool cold = !warm;
+    if (on && warm) {
+        L.start_newton(z0, p_init, rs, ri0, ri1, false);
+        L.may_damp = false;
+    } else if (on) {
+        L.start(m, z0, p_init);
+    }
+    int evals = 0;
+    for (int guard = 0; guard < 2 * BD_EVAL_GUARD + robust_eval_budget<DEW>(); guard++) {
+        if (__ballot(!L.done()) == 0ull) break;
+        if (L.done()) continue;
+        double e0, e1;
+        L.point(e0, e1);
+        PhaseEval e = phase_eval(m, e0, e1);  // the only evaluation site
+        L.consume(m, e);
+        if (++evals >= (L.robust ? robust_eval_budget<DEW>() : BD_EVAL_GUARD) && !L.done()) L.idle();  // rc = BD_FAILED
+        if (L.done() && L.rc != BD_OK) {
+            if (!cold) {
+                cold = true;
+                L.start(m, z0, p_init);
+                evals = 0;
+            } else if (!L.robust && L.root_failed) {
+                L.start(m, z0, p_init, SS_MAX_IT, NEWTON_MAX_IT, true);
+                evals = 0;
+            }
+        }
+    }
+    const bool ok = on && L.done() && L.rc == BD_OK;
+    if (ok) out = L.out;
+    return ok ? BD_OK : BD_FAILED;
+}
+
 }  // namespace pcs

@@ -446,6 +446,28 @@ def mix_bubble_dew(params, kij, temperature, molefracs, pressure, dew, want_iter
     return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
 
 
+def mix_bubble_dew_temperature(params, kij, pressure, molefracs, temperature, dew, want_iters=False, workspace=True):
+    """Bubble (dew=False) / dew (dew=True) temperatures at `pressure` [Pa] from the first iterate `temperature` [K]
+    (pcs_mix_bubble_dew_temperature).  workspace=False: rows bucketed by class inside each workgroup instead of the
+    batch-wide class order (same results).
+    -> dict(t [K], rho4 [n,4] A^-3 = (rhoV_1, rhoV_2, rhoL_1, rhoL_2) at t, status bool (True = failed), iters int32 or None)."""
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    pressure = _prep(pressure, device)
+    molefracs = _prep(molefracs, device)
+    temperature = _prep(temperature, device)
+    n = params.shape[0]
+    _same_rows(n, kij=kij, pressure=pressure, molefracs=molefracs, temperature=temperature)
+    t, rho4 = _news(device, n, (n, 4))
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
+    ws = _workspace(n, device) if workspace else None
+    _call(device, "pcs_mix_bubble_dew_temperature", int(bool(dew)), params, kij, pressure, molefracs, temperature, n, t, rho4,
+          status, iters, ws)
+    return {"t": t, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
+
+
 def mix_derivatives(params, kij, temperature, density):
     """(a [n], p [n], mu [n,2], v [n,2]) — PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420)."""
     device = _device_of(params)

@@ -52,6 +52,44 @@ class _BubbleDew(torch.autograd.Function):
         return (None, *_shell.scatter(ctx.comp, jac, g_value, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None)
 
 
+_T_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, pressure in the [n,19] quotient
+
+
+class _BubbleDewTemperature(torch.autograd.Function):
+    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for the solve
+    (csrc/mix_temperature.hip), then as _BubbleDew: one compaction plan, gathers only when rows were dropped.  Gradient by the
+    implicit-function theorem on p(theta, T) = p_spec with J = pcs_mix_jacobian at the solved state:
+    dT/dtheta = -J[:, :18] / J[:, 18], dT/dp_spec = 1 / J[:, 18] (elementwise on the kept rows)."""
+
+    @staticmethod
+    def forward(ctx, dew, parameters, kij, pressure, molefracs, temperature, check=False):
+        dev = native._device_of(parameters)
+        par = native._prep(parameters, dev, (2, 8))
+        k = native._prep(kij, dev, (2,))
+        r = native.mix_bubble_dew_temperature(par, k, native._prep(pressure, dev), native._prep(molefracs, dev),
+                                              native._prep(temperature, dev), dew)
+        comp = native.Compaction(r["status"])
+        value = comp.gather(r["t"])
+        ctx.needs = list(ctx.needs_input_grad[1:4])
+        if any(ctx.needs):
+            jac = native.mix_jacobian(comp.gather(par), comp.gather(k), value, comp.gather(r["rho4"]), dew)
+            inv = 1.0 / jac[:, 18:19]
+            ctx.save_for_backward(torch.cat((-jac[:, :18] * inv, inv), dim=1))
+            ctx.comp = comp
+        ctx.in_devices = (parameters.device, kij.device, pressure.device)
+        flags = ()
+        if check:
+            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
+                comp.gather(par), comp.gather(k), value, feed)),)
+        return (*_shell.finish(ctx, parameters.device, [value], r["status"], *flags), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, *_g_flags):
+        (quot,) = ctx.saved_tensors
+        return (None, *_shell.scatter(ctx.comp, quot, g_value, _T_COLUMNS, ctx.needs, ctx.in_devices), None, None, None)
+
+
 class _MixDerivatives(torch.autograd.Function):
     """(a, p, mu, v) = derivatives(parameters[n,2,8], kij[n,2], temperature[n], density[n,2]) with gradients to all four
     inputs (feos_torch/pcsaft_mix.py:31-154, :395-420 are torch graphs in the reference)."""
@@ -176,6 +214,33 @@ class PcSaftMix(_shell.Reducible):
         """(p [Pa], nans) at T [K], vapour mole fraction of component 1, initial pressure [Pa] (:446-468).
         check_stability=True: (p, nans, stable) with the stability of the vapour at the solution (see bubble_point)."""
         return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
+
+    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False):
+        if self.ncomp != 2:
+            raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
+        # the mole fractions do not enter the reference's final formula and the first iterate only starts the search: no
+        # gradient flows to either
+        *out, comp = _BubbleDewTemperature.apply(dew, self._par, self.kij, torch.as_tensor(pressure, dtype=torch.float64),
+                                                 _detached(molefracs), _detached(temperature), bool(check_stability))
+        self._reduce(comp)
+        return tuple(out)
+
+    def bubble_temperature(self, pressure, liquid_molefracs, temperature, check_stability=False):
+        """(T [K], nans): the temperature at which the liquid of mole fraction `liquid_molefracs` (component 1) starts to boil
+        at `pressure` [Pa], i.e. bubble_point(T, x, .) = pressure, solved in one kernel (csrc/mix_temperature.hpp) from the
+        mandatory first iterate `temperature` [K].  Values for the converged rows only, the model is reduced like
+        bubble_point does.  Differentiable w.r.t. parameters, kij and pressure (implicit-function theorem on the pressure
+        Jacobian: dT/dp = 1 / (dp/dT)); mole fractions and first iterate receive no gradient.  A row fails where no trial
+        temperature near the first iterate has an equilibrium, where the pressure lies above the bubble line, or on a branch
+        on which the pressure falls with the temperature (include/pcsaft_hip.h, pcs_mix_bubble_dew_temperature).
+        check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class."""
+        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability)
+
+    def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False):
+        """(T [K], nans): the temperature at which the vapour of mole fraction `vapor_molefracs` starts to condense at
+        `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
+        such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution."""
+        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's

@@ -252,6 +252,39 @@ int pcs_mix_bubble_dew(int dew, const double* params, const double* kij, const d
                        void* workspace, void* stream);
 
 /*
+ * Binary-mixture bubble (dew = 0) / dew (dew = 1) TEMPERATURE at a given pressure: the T with p_bubble(T, z) = p_spec
+ * (resp. p_dew), the inverse of pcs_mix_bubble_dew in its temperature argument, with the partial densities of both phases at
+ * that T.  Safeguarded Newton on f = ln p(T) - ln p_spec in 1/T inside one kernel (csrc/mix_temperature.hpp): every trial is
+ * the bubble / dew solve of pcs_mix_bubble_dew at the trial temperature with the initial pressure p_spec -- cold at the first
+ * iterate, from the densities of the last solved trial afterwards --, p(T) is that solve's pressure, and the slope
+ * d ln p / dT is a temperature tangent at fixed densities.  The reference has no counterpart.
+ *   params  [n,2,8] in   (16-byte aligned)
+ *   kij     [n,2]   in   (16-byte aligned) as for pcs_mix_bubble_dew
+ *   p_spec  [n]     in   Pa, the specified pressure
+ *   z       [n]     in   mole fraction of component 1 in the specified phase (liquid for bubble, vapour for dew), 0 < z < 1
+ *   t_init  [n]     in   K, the first iterate (mandatory, as the initial pressure of pcs_mix_bubble_dew is)
+ *   t_out   [n]     out  K     (optional)
+ *   rho4    [n,4]   out  A^-3 (rhoV_1, rhoV_2, rhoL_1, rhoL_2) at t_out: what pcs_mix_jacobian needs (optional, 16-byte aligned)
+ *   status  [n]     out  uint8, 1 = failed; outputs of such rows are 0.  A row fails AT ONCE when p_spec or t_init is
+ *                        non-finite or <= 0, z is non-finite or outside 0 < z < 1, or a parameter or kij entry is non-finite;
+ *                        otherwise when: no trial finds an equilibrium at t_init nor at 8 temperatures below it (each lower
+ *                        by a factor 1.1); p_spec lies above the highest pressure of the line (the bracket between a solved
+ *                        trial and one without an equilibrium closes to 1e-6); a solved trial has a slope d ln p / dT that is
+ *                        not positive and finite -- the retrograde dew branch near a mixture critical point, where the
+ *                        pressure falls with the temperature, is not served --; or after 40 trials.
+ *                        Accepted: |ln p(T) - ln p_spec| <= 1e-12, or <= 1e-11 directly after a trial within 1e-8 (rounding
+ *                        floor of the inner solve); d ln p / d ln T > 1 on these lines, so T is at least as good.
+ *   iters   [n]     out  int32 trial temperatures used, -1 for failed rows (optional, diagnostics)
+ *   workspace            optional device scratch of pcs_workspace_bytes(n): the rows are then taken in batch-wide class
+ *                        order (class-uniform waves); results are identical.  One row per lane, no work queue.
+ * A row's result does not depend on the rows it shares a wave with.  Backward pass: J = pcs_mix_jacobian at (t_out, rho4);
+ * implicit-function theorem on p(theta, T) = p_spec:  dT/dtheta = -J[:, :18] / J[:, 18],  dT/dp_spec = 1 / J[:, 18].
+ */
+int pcs_mix_bubble_dew_temperature(int dew, const double* params, const double* kij, const double* p_spec, const double* z,
+                                   const double* t_init, int64_t n, double* t_out, double* rho4, uint8_t* status,
+                                   int32_t* iters, void* workspace, void* stream);
+
+/*
  * PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420) at given partial densities rho [n,2]:
  * a [n], p [n] (reduced), residual chemical potentials mu [n,2], partial molar volumes v [n,2].
  * Any output may be NULL.

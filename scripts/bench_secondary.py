@@ -11,6 +11,9 @@ with HIP events on the launch stream, inputs resident in HBM.
            vapour pressures, vapor_pressure alongside)
   enthalpy: PcSaftPure.enthalpy_of_vaporization kernels, batch 1e6 and 1e7 (forward, forward + backward, vapor_pressure and
             the all-fp64 VLE solve pcs_pure_vle_fp64 alongside, failed rows by class)
+  mix_temperature: PcSaftMix.bubble_temperature / dew_temperature kernel (pcs_mix_bubble_dew_temperature), batch 1e6 minus the
+            rows bubble_point / dew_point fail on, at the pressures those give at the batch temperatures, started 5 % below
+            the answer; bubble_point / dew_point alongside, trial histogram and failed rows
 Prints one JSON object per config."""
 import json
 import os
@@ -185,3 +188,21 @@ if "enthalpy" in which:
                           "ms_forward_backward": ms_fb, "ms_vapor_pressure": ms_vp, "ms_vle_fp64": ms_vle, "failed": int(failed.sum()),
                           "failed_by_class": by_class, "failed_vapor_pressure": int(vp["status"].sum()),
                           "failed_here_only": int((failed & ~vp["status"]).sum())}))
+if "mix_temperature" in which:
+    # bubble / dew temperatures of the mix_batch rows at the pressures bubble_point / dew_point give at the batch temperatures
+    # (so every solved row has an answer: the batch temperature), started 5 % below it.  One row per lane, no work queue: a
+    # wave pays its slowest row, unlike the pressure solve it is reported next to
+    n = 1_000_000
+    P, K, T, X, PI = mix_batch(n)
+    a = [d(v) for v in (P, K, T, X, PI)]
+    for dew in (False, True):
+        ms_p, rp = timed(lambda: native.mix_bubble_dew(*a, dew), reps=3)
+        keep = torch.nonzero(~rp["status"]).view(-1)
+        Pk, Kk, Tk, Xk, pk = a[0][keep].contiguous(), a[1][keep].contiguous(), a[2][keep].contiguous(), a[3][keep].contiguous(), rp["p"][keep].contiguous()
+        T0 = 0.95 * Tk
+        ms, r = timed(lambda: native.mix_bubble_dew_temperature(Pk, Kk, pk, Xk, T0, dew, want_iters=True), reps=3)
+        ok = ~r["status"]
+        err = ((r["t"][ok] / Tk[ok]) - 1.0).abs()
+        print(json.dumps({"config": f"PcSaftMix {'dew' if dew else 'bubble'} temperature batch={len(keep)}", "ms": ms, "rows_per_s": len(keep) / ms * 1e3,
+                          "ms_pressure_solve_1e6": ms_p, "failed": int(r["status"].sum()), "trials": torch.bincount(r["iters"][ok].long()).tolist(),
+                          "round_trip_above_1e-9": int((err > 1e-9).sum()), "median_rel_round_trip": float(err.median())}))
