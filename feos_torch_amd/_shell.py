@@ -13,8 +13,8 @@ def finish(ctx, out_device, values, nans, *flags):
 
 def scatter(comp, jac, g, table, needs, devices):
     """Backward of a property: per needed input g_j * jac[j, columns] in the row of the j-th kept row (zeros in dropped rows,
-    one kernel each), on that input's device."""
-    g = g.to(comp.device).contiguous()
+    one kernel each), on that input's device.  g None: jac carries the upstream gradients already."""
+    g = None if g is None else g.to(comp.device).contiguous()
     return [comp.expand(jac, g, col0, ncol).view(shape).to(dev) if need else None
             for (col0, ncol, shape), need, dev in zip(table, needs, devices)]
 

@@ -559,6 +559,26 @@ def mix_jacobian(params, kij, temperature, rho4, dew):
     return jac
 
 
+def mix_point_jacobian(params, kij, temperature, rho4, dew, want_p=True, want_y=True):
+    """(jac_p [n,19] or None, jac_y [n,19] or None): gradients of the bubble/dew pressure [Pa] and of the incipient phase's
+    mole fraction of component 1 w.r.t. (params[0,:], params[1,:], kij[0], kij[1], T), one kernel for both
+    (pcs_mix_point_jacobian)."""
+    if not (want_p or want_y):
+        raise ValueError("at least one of want_p / want_y is required")
+    device = rho4.device
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    rho4 = _prep(rho4, device, (4,))
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij, rho4=rho4)
+    jac_p = _new(device, (n, 19)) if want_p else None
+    jac_y = _new(device, (n, 19)) if want_y else None
+    ws = _workspace(n, device)
+    _call(device, "pcs_mix_point_jacobian", int(bool(dew)), params, kij, temperature, rho4, n, jac_p, jac_y, ws)
+    return jac_p, jac_y
+
+
 # ------------------------------------------------------------------------------------------
 # heterosegmented gc-PC-SAFT
 # ------------------------------------------------------------------------------------------

@@ -19,22 +19,53 @@ from .native import _detached
 _COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, temperature in the [n,19] Jacobian
 
 
+def _incipient_molefrac(rho4, dew):
+    """y [n]: mole fraction of component 1 in the incipient phase (vapour for bubble, liquid for dew) of rho4 [n,4]"""
+    inc = rho4[:, 2:4] if dew else rho4[:, 0:2]
+    return inc[:, 0] / (inc[:, 0] + inc[:, 1])
+
+
+def _weighted(blocks, grads):
+    """sum of g[:, None] * block over the upstream gradients that are present (at least one is) -> (Jacobian, g) for
+    _shell.scatter: a single block keeps its g for the fused product of the scatter kernel"""
+    present = [(b, g.to(b.device)) for b, g in zip(blocks, grads) if g is not None]
+    if len(present) == 1:
+        return present[0]
+    return sum(g[:, None] * b for b, g in present), None
+
+
+def _outputs(ctx, device, values, status, flags, comp):
+    """(value, nans[, stable][, y], plan): _shell.finish, then the incipient composition moved behind the flags"""
+    out = _shell.finish(ctx, device, values, status, *flags)
+    return (out[0], *out[len(values):], *out[1:len(values)], comp)
+
+
 class _BubbleDew(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew pressure.  Dense solve, one compaction plan (its 4-byte row
-    count is the call's only host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the
-    reference drops them inside the native call, src/pcsaft.rs:216-231)."""
+    """value[n_ok], nans[n][, stable[n_ok]][, y[n_ok]], plan = bubble / dew pressure.  Dense solve, one compaction plan (its
+    4-byte row count is the call's only host synchronisation), single-kernel gathers only when rows were dropped
+    (native.Compaction; the reference drops them inside the native call, src/pcsaft.rs:216-231).  incipient: y = mole fraction
+    of component 1 in the incipient phase, differentiable like the pressure; the backward pass then takes both Jacobian
+    blocks from ONE pcs_mix_point_jacobian call instead of pcs_mix_jacobian."""
 
     @staticmethod
-    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, check=False):
+    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, check=False, incipient=False):
         dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (2, 8))
         k = native._prep(kij, dev, (2,))
         T = native._prep(temperature, dev)
         r = native.mix_bubble_dew(par, k, T, native._prep(molefracs, dev), native._prep(pressure, dev), dew)
         comp = native.Compaction(r["status"])
-        value = comp.gather(r["p"])
+        values = [comp.gather(r["p"])]
         ctx.needs = list(ctx.needs_input_grad[1:4])
-        if any(ctx.needs):
+        ctx.incipient = incipient
+        if incipient:
+            rho4 = comp.gather(r["rho4"])
+            values.append(_incipient_molefrac(rho4, dew))
+            ctx.set_materialize_grads(False)  # either upstream gradient may be absent
+            if any(ctx.needs):
+                ctx.save_for_backward(*native.mix_point_jacobian(comp.gather(par), comp.gather(k), comp.gather(T), rho4, dew))
+                ctx.comp = comp
+        elif any(ctx.needs):
             jac = native.mix_jacobian(comp.gather(par), comp.gather(k), comp.gather(T), comp.gather(r["rho4"]), dew)
             ctx.save_for_backward(jac)
             ctx.comp = comp
@@ -43,26 +74,33 @@ class _BubbleDew(torch.autograd.Function):
         if check:
             flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
                 comp.gather(par), comp.gather(k), comp.gather(T), feed)),)
-        return (*_shell.finish(ctx, parameters.device, [value], r["status"], *flags), comp)
+        return _outputs(ctx, parameters.device, values, r["status"], flags, comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, *_g_flags):
-        (jac,) = ctx.saved_tensors
-        return (None, *_shell.scatter(ctx.comp, jac, g_value, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None)
+    def backward(ctx, g_value, *g_rest):
+        if ctx.incipient:
+            if g_value is None and g_rest[-2] is None:
+                return (None,) * 8
+            jac, g = _weighted(ctx.saved_tensors, (g_value, g_rest[-2]))  # outputs: value, nans[, stable], y, plan
+        else:
+            (jac,), g = ctx.saved_tensors, g_value
+        return (None, *_shell.scatter(ctx.comp, jac, g, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None)
 
 
 _T_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, pressure in the [n,19] quotient
 
 
 class _BubbleDewTemperature(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for the solve
-    (csrc/mix_temperature.hip), then as _BubbleDew: one compaction plan, gathers only when rows were dropped.  Gradient by the
-    implicit-function theorem on p(theta, T) = p_spec with J = pcs_mix_jacobian at the solved state:
-    dT/dtheta = -J[:, :18] / J[:, 18], dT/dp_spec = 1 / J[:, 18] (elementwise on the kept rows)."""
+    """value[n_ok], nans[n][, stable[n_ok]][, y[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for
+    the solve (csrc/mix_temperature.hip), then as _BubbleDew: one compaction plan, gathers only when rows were dropped.
+    Gradient by the implicit-function theorem on p(theta, T) = p_spec with J = pcs_mix_jacobian at the solved state:
+    dT/dtheta = -J[:, :18] / J[:, 18], dT/dp_spec = 1 / J[:, 18] (elementwise on the kept rows).  incipient: y as for
+    _BubbleDew, followed along the same line with (J_p, J_y) from ONE pcs_mix_point_jacobian call:
+    dy/dtheta|_p = J_y[:, :18] - J_y[:, 18] J_p[:, :18] / J_p[:, 18], dy/dp_spec = J_y[:, 18] / J_p[:, 18]."""
 
     @staticmethod
-    def forward(ctx, dew, parameters, kij, pressure, molefracs, temperature, check=False):
+    def forward(ctx, dew, parameters, kij, pressure, molefracs, temperature, check=False, incipient=False):
         dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (2, 8))
         k = native._prep(kij, dev, (2,))
@@ -70,8 +108,21 @@ class _BubbleDewTemperature(torch.autograd.Function):
                                               native._prep(temperature, dev), dew)
         comp = native.Compaction(r["status"])
         value = comp.gather(r["t"])
+        values = [value]
         ctx.needs = list(ctx.needs_input_grad[1:4])
-        if any(ctx.needs):
+        ctx.incipient = incipient
+        if incipient:
+            rho4 = comp.gather(r["rho4"])
+            values.append(_incipient_molefrac(rho4, dew))
+            ctx.set_materialize_grads(False)
+            if any(ctx.needs):
+                jac_p, jac_y = native.mix_point_jacobian(comp.gather(par), comp.gather(k), value, rho4, dew)
+                inv = 1.0 / jac_p[:, 18:19]
+                dy_dp = jac_y[:, 18:19] * inv
+                ctx.save_for_backward(torch.cat((-jac_p[:, :18] * inv, inv), dim=1),
+                                      torch.cat((jac_y[:, :18] - dy_dp * jac_p[:, :18], dy_dp), dim=1))
+                ctx.comp = comp
+        elif any(ctx.needs):
             jac = native.mix_jacobian(comp.gather(par), comp.gather(k), value, comp.gather(r["rho4"]), dew)
             inv = 1.0 / jac[:, 18:19]
             ctx.save_for_backward(torch.cat((-jac[:, :18] * inv, inv), dim=1))
@@ -81,13 +132,18 @@ class _BubbleDewTemperature(torch.autograd.Function):
         if check:
             flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
                 comp.gather(par), comp.gather(k), value, feed)),)
-        return (*_shell.finish(ctx, parameters.device, [value], r["status"], *flags), comp)
+        return _outputs(ctx, parameters.device, values, r["status"], flags, comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, *_g_flags):
-        (quot,) = ctx.saved_tensors
-        return (None, *_shell.scatter(ctx.comp, quot, g_value, _T_COLUMNS, ctx.needs, ctx.in_devices), None, None, None)
+    def backward(ctx, g_value, *g_rest):
+        if ctx.incipient:
+            if g_value is None and g_rest[-2] is None:
+                return (None,) * 8
+            quot, g = _weighted(ctx.saved_tensors, (g_value, g_rest[-2]))
+        else:
+            (quot,), g = ctx.saved_tensors, g_value
+        return (None, *_shell.scatter(ctx.comp, quot, g, _T_COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None)
 
 
 class _MixDerivatives(torch.autograd.Function):
@@ -194,38 +250,44 @@ class PcSaftMix(_shell.Reducible):
             return _MixnDerivatives.apply(self._par, temperature, density)
         return _MixDerivatives.apply(self._par, self.kij, temperature, density)
 
-    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
+    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False, incipient_molefracs=False):
         if self.ncomp != 2:
             raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
         # mole fractions and initial pressure do not enter the reference's final formula (:435-444): no gradient flows to them
         *out, comp = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure),
-                                      bool(check_stability))
+                                      bool(check_stability), bool(incipient_molefracs))
         self._reduce(comp)
         return tuple(out)
 
-    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
+    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False, incipient_molefracs=False):
         """(p [Pa], nans) at T [K], liquid mole fraction of component 1, initial pressure [Pa] (:422-444).
         check_stability=True: (p, nans, stable), stable [bool, aligned with p] = the liquid at the solution passed
         stability_analysis (False: a metastable or unstable root, e.g. inside a liquid-liquid split).  p, nans, the gradients
-        and the model reduction are those of the default call."""
-        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability)
+        and the model reduction are those of the default call.
+        incipient_molefracs=True: the tuple gains a LAST element y [float64, aligned with p], the mole fraction of component 1
+        in the incipient vapour -- (p, nans, y) or (p, nans, stable, y) -- differentiable w.r.t. parameters, kij and
+        temperature like p (both gradients from one kernel, pcs_mix_point_jacobian); the other elements are those of the
+        default call, bit for bit.  Not part of the reference's class."""
+        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability, incipient_molefracs)
 
-    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False):
+    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False, incipient_molefracs=False):
         """(p [Pa], nans) at T [K], vapour mole fraction of component 1, initial pressure [Pa] (:446-468).
-        check_stability=True: (p, nans, stable) with the stability of the vapour at the solution (see bubble_point)."""
-        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
+        check_stability=True: (p, nans, stable) with the stability of the vapour at the solution (see bubble_point).
+        incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid (see bubble_point)."""
+        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability, incipient_molefracs)
 
-    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False):
+    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False, incipient_molefracs=False):
         if self.ncomp != 2:
             raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
         # the mole fractions do not enter the reference's final formula and the first iterate only starts the search: no
         # gradient flows to either
         *out, comp = _BubbleDewTemperature.apply(dew, self._par, self.kij, torch.as_tensor(pressure, dtype=torch.float64),
-                                                 _detached(molefracs), _detached(temperature), bool(check_stability))
+                                                 _detached(molefracs), _detached(temperature), bool(check_stability),
+                                                 bool(incipient_molefracs))
         self._reduce(comp)
         return tuple(out)
 
-    def bubble_temperature(self, pressure, liquid_molefracs, temperature, check_stability=False):
+    def bubble_temperature(self, pressure, liquid_molefracs, temperature, check_stability=False, incipient_molefracs=False):
         """(T [K], nans): the temperature at which the liquid of mole fraction `liquid_molefracs` (component 1) starts to boil
         at `pressure` [Pa], i.e. bubble_point(T, x, .) = pressure, solved in one kernel (csrc/mix_temperature.hpp) from the
         mandatory first iterate `temperature` [K].  Values for the converged rows only, the model is reduced like
@@ -233,14 +295,17 @@ class PcSaftMix(_shell.Reducible):
         Jacobian: dT/dp = 1 / (dp/dT)); mole fractions and first iterate receive no gradient.  A row fails where no trial
         temperature near the first iterate has an equilibrium, where the pressure lies above the bubble line, or on a branch
         on which the pressure falls with the temperature (include/pcsaft_hip.h, pcs_mix_bubble_dew_temperature).
-        check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class."""
-        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability)
+        check_stability=True: (T, nans, stable) as for bubble_point.  incipient_molefracs=True: a last element y [aligned with
+        T], the mole fraction of component 1 in the incipient vapour at the solution, differentiable w.r.t. parameters, kij and
+        pressure along the line p(theta, T) = pressure.  Not part of the reference's class."""
+        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability, incipient_molefracs)
 
-    def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False):
+    def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False, incipient_molefracs=False):
         """(T [K], nans): the temperature at which the vapour of mole fraction `vapor_molefracs` starts to condense at
         `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
-        such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution."""
-        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability)
+        such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution.
+        incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid."""
+        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability, incipient_molefracs)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's

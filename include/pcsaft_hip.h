@@ -349,6 +349,29 @@ int pcs_mix_jacobian(int dew, const double* params, const double* kij, const dou
                      int64_t n, double* jac, void* workspace, void* stream);
 
 /*
+ * Gradients of TWO functionals of a converged bubble (dew = 0) / dew (dew = 1) point in one kernel (ABI 111): the pressure,
+ * as pcs_mix_jacobian, and the composition of the INCIPIENT phase.  Inputs as pcs_mix_jacobian: (temp, rho4) are the state
+ * pcs_mix_bubble_dew or pcs_mix_bubble_dew_temperature returned.
+ *   jac_p [n,19]  out  d p / d (params[0,0..7], params[1,0..7], kij[0], kij[1], T), Pa per unit (optional)
+ *   jac_y [n,19]  out  d y / d (the same 19), y = the mole fraction of COMPONENT 1 in the incipient phase -- the vapour for
+ *                      bubble, y = rhoV_1 / (rhoV_1 + rhoV_2), the liquid for dew, y = rhoL_1 / (rhoL_1 + rhoL_2) -- at fixed
+ *                      composition of the specified phase (optional)
+ * Either output may be NULL, not both (error).  y has no explicit dependence on the inputs: with u = (ln rho_spec,
+ * ln rho_inc_1, ln rho_inc_2) and F = (mu_1^S - mu_1^I, mu_2^S - mu_2^I, p^S - p^I) = 0,  dy/dtheta = -w . dF/dtheta|_u with
+ * J^T w = dy/du = (0, y (1 - y), -y (1 - y)); the coefficient set, both phase evaluations and the elimination of J^T are
+ * shared with the pressure gradient (csrc/mix_incipient.hpp).  A row whose 3x3 system is singular gets NaN in its outputs;
+ * rows with rho4 = 0 (failed rows of the solve) get unspecified values and do not disturb the others.
+ * workspace: device scratch of pcs_workspace_bytes(n) or NULL, as pcs_mix_jacobian (batch-wide class order; results are
+ * identical).  A row's result does not depend on its wave mates, on n, on the workspace or on which outputs are requested.
+ * Along a line of constant pressure (backward pass of pcs_mix_bubble_dew_temperature with the composition), from the two
+ * blocks at (t_out, rho4), by the implicit-function theorem on p(theta, T) = p_spec:
+ *   dT/dtheta = -jac_p[:, :18] / jac_p[:, 18],                          dT/dp_spec = 1 / jac_p[:, 18]
+ *   dy/dtheta|_p = jac_y[:, :18] - jac_y[:, 18] jac_p[:, :18] / jac_p[:, 18],   dy/dp_spec = jac_y[:, 18] / jac_p[:, 18]
+ */
+int pcs_mix_point_jacobian(int dew, const double* params, const double* kij, const double* temp, const double* rho4,
+                           int64_t n, double* jac_p, double* jac_y, void* workspace, void* stream);
+
+/*
  * ---- heterosegmented gc-PC-SAFT (binary mixtures) -----------------------------------------
  * Replaces the reference's stateful GcPcSaft class (src/gc_pcsaft.rs:15-99: segment records,
  * per-row chemical records, binary segment records, phi) and the Python tails of

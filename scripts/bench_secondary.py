@@ -14,6 +14,9 @@ with HIP events on the launch stream, inputs resident in HBM.
   mix_temperature: PcSaftMix.bubble_temperature / dew_temperature kernel (pcs_mix_bubble_dew_temperature), batch 1e6 minus the
             rows bubble_point / dew_point fail on, at the pressures those give at the batch temperatures, started 5 % below
             the answer; bubble_point / dew_point alongside, trial histogram and failed rows
+  mix_incipient: the backward kernels of bubble_point / dew_point on the converged rows of config 4: pcs_mix_jacobian (pressure
+            gradient, the default) next to pcs_mix_point_jacobian with the pressure block only, the composition block only and
+            both (incipient_molefracs=True); the fused call has to cost less than two pcs_mix_jacobian launches
 Prints one JSON object per config."""
 import json
 import os
@@ -206,3 +209,20 @@ if "mix_temperature" in which:
         print(json.dumps({"config": f"PcSaftMix {'dew' if dew else 'bubble'} temperature batch={len(keep)}", "ms": ms, "rows_per_s": len(keep) / ms * 1e3,
                           "ms_pressure_solve_1e6": ms_p, "failed": int(r["status"].sum()), "trials": torch.bincount(r["iters"][ok].long()).tolist(),
                           "round_trip_above_1e-9": int((err > 1e-9).sum()), "median_rel_round_trip": float(err.median())}))
+if "mix_incipient" in which:
+    # gradients at the converged rows of mix_batch(1e6), both problems, median of 3 in this process.  "both" shares the
+    # coefficient set, the two phase evaluations and the 3x3 elimination between the blocks; the adjoint passes are per block
+    n = 1_000_000
+    P, K, T, X, PI = mix_batch(n)
+    a = [d(v) for v in (P, K, T, X, PI)]
+    for dew in (False, True):
+        r = native.mix_bubble_dew(*a, dew)
+        keep = torch.nonzero(~r["status"]).view(-1)
+        Pk, Kk, Tk, rk = a[0][keep].contiguous(), a[1][keep].contiguous(), a[2][keep].contiguous(), r["rho4"][keep].contiguous()
+        ms_jac, _ = timed(lambda: native.mix_jacobian(Pk, Kk, Tk, rk, dew), reps=3)
+        ms_p, _ = timed(lambda: native.mix_point_jacobian(Pk, Kk, Tk, rk, dew, want_y=False), reps=3)
+        ms_y, _ = timed(lambda: native.mix_point_jacobian(Pk, Kk, Tk, rk, dew, want_p=False), reps=3)
+        ms_both, _ = timed(lambda: native.mix_point_jacobian(Pk, Kk, Tk, rk, dew), reps=3)
+        print(json.dumps({"config": f"PcSaftMix {'dew' if dew else 'bubble'} point gradients batch={len(keep)}", "ms_mix_jacobian": ms_jac,
+                          "ms_point_jacobian_p": ms_p, "ms_point_jacobian_y": ms_y, "ms_point_jacobian_both": ms_both,
+                          "both_over_two_mix_jacobian": ms_both / (2.0 * ms_jac), "fused_pays": bool(ms_both < 2.0 * ms_jac)}))
