@@ -438,6 +438,51 @@ int orc_mixn_derivatives(const double* params, const double* T, const double* rh
     return bad;
 }
 
+// Exact gradient of L_i = ga a + gp p + gmu . mu + gv . v (n-component PcSaftMix.derivatives at one state point per row) with
+// respect to every input of the row: grad [n, 9 nc + 1] = dL_i/d(parameters [nc][8], T, rho [nc]).  Nested duals: the
+// HyperDual<., 7> of derivatives_mixn over DualN<F, 8>, whose eight tangents are one block of the 9 nc + 1 input directions per
+// pass (parameters, T and densities are all seeded alike: oracle/pcsaft_mixn.hpp is generic in the parameter type).
+// prec = 1: F = long double throughout, rounded to double only when the gradient is stored -- the referee.  prec = 0: the same
+// code in double -- what an fp64 evaluation of the same formulas can deliver, the yardstick of the tests' bars.
+// The formula differentiated is the one the REAL parts select (polar? associating? min(m, 2)), so the mu column of a
+// non-polar component is exactly 0, kappa_ab / epsilon_k_ab / na / nb of a site-less component next to an associating one
+// have the derivative of the sums they enter (:211-218), and every association column of a row without sites is 0.
+// Returns 1 if a row asks for two associating components or nc is out of range, as orc_mixn_derivatives.
+int orc_mixn_derivatives_vjp_exact(const double* params, const double* T, const double* rho, int nc, int64_t n, int prec,
+                                   const double* ga, const double* gp, const double* gmu, const double* gv, double* grad) {
+    if (nc < 1 || nc > MIXN_MAX) return 1;
+    const int D = 9 * nc + 1;
+    int bad = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(| : bad)
+    for (int64_t i = 0; i < n; i++) {
+        auto run = [&](auto zero) {
+            typedef decltype(zero) F;
+            constexpr int K = 8;
+            typedef DualN<F, K> G;
+            for (int d0 = 0; d0 < D; d0 += K) {
+                auto seed = [&](double x, int dir) {
+                    G g(0.0);
+                    g.re = F(x);
+                    if (dir >= d0 && dir < d0 + K) g.eps[dir - d0] = F(1);
+                    return g;
+                };
+                G par[8 * MIXN_MAX], r[MIXN_MAX], aa, pp, m2[MIXN_MAX], v2[MIXN_MAX];
+                for (int k = 0; k < 8 * nc; k++) par[k] = seed(params[8 * nc * i + k], k);
+                for (int k = 0; k < nc; k++) r[k] = seed(rho[nc * i + k], 8 * nc + 1 + k);
+                if (!derivatives_mixn<G, G>(nc, par, seed(T[i], 8 * nc), r, aa, pp, m2, v2)) bad |= 1;
+                for (int k = 0; k < K && d0 + k < D; k++) {
+                    F e = F(ga[i]) * aa.eps[k] + F(gp[i]) * pp.eps[k];
+                    for (int c = 0; c < nc; c++) e += F(gmu[nc * i + c]) * m2[c].eps[k] + F(gv[nc * i + c]) * v2[c].eps[k];
+                    grad[(size_t)D * i + d0 + k] = double(e);
+                }
+            }
+        };
+        if (prec == 1) run((long double)0);
+        else run(double(0));
+    }
+    return bad;
+}
+
 // PcSaftMix.derivatives in long double with the safeguarded association iterations and the cancellation-free site
 // fractions: the exact values of the model, against which both the kernels and the reference's own fp64 evaluation
 // (orc_mix_derivatives, robust = 0) are measured row by row.

@@ -99,6 +99,8 @@ def lib():
         L.orc_mix_bubble_dew_grad.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p]
         L.orc_mixn_derivatives.argtypes = [_f64p, _f64p, _f64p, _int, _i64, _int, _f64p, _f64p, _f64p, _f64p]
         L.orc_mixn_derivatives.restype = _int
+        L.orc_mixn_derivatives_vjp_exact.argtypes = [_f64p, _f64p, _f64p, _int, _i64, _int, _f64p, _f64p, _f64p, _f64p, _f64p]
+        L.orc_mixn_derivatives_vjp_exact.restype = _int
         L.orc_mix_derivatives_ld.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p, _f64p]
         L.orc_mix_bubble_dew_grad_ld.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p]
         L.orc_mix_bubble_dew_continuation.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _f64p, _f64p, _i32p, _i32p]
@@ -264,6 +266,21 @@ def mixn_derivatives(params, T, rho, prec=0):
     if lib().orc_mixn_derivatives(params, T, rho, nc, n, int(prec), a, p, mu, v):
         raise Exception("Only up to two associating components are allowed, and two only for binary mixtures!")
     return a, p, mu, v
+
+
+def mixn_derivatives_vjp_exact(params, T, rho, ga, gp, gmu, gv, prec=1):
+    """Gradient of L_i = ga_i a_i + gp_i p_i + gmu_i . mu_i + gv_i . v_i (n-component PcSaftMix.derivatives) by nested duals:
+    grad [n, 9 nc + 1] = dL_i/d(parameters [nc][8], T, rho [nc]), every column seeded (site counts and zero-valued entries
+    included: the derivative of the formula that the row's real parts select).  prec=1: long double throughout, rounded to
+    double on return -- the referee; prec=0: the same code in double, the yardstick for what fp64 can deliver."""
+    params, T, rho = _c(params), _c(T), _c(rho)
+    n, nc = rho.shape
+    assert params.shape == (n, nc, 8)
+    ga, gp, gmu, gv = _c(ga, (n,)), _c(gp, (n,)), _c(gmu, (n, nc)), _c(gv, (n, nc))
+    grad = np.empty((n, 9 * nc + 1))
+    if lib().orc_mixn_derivatives_vjp_exact(params, T, rho, nc, n, int(prec), ga, gp, gmu, gv, grad):
+        raise Exception("Only up to two associating components are allowed, and two only for binary mixtures!")
+    return grad
 
 
 def mix_helmholtz(params, kij, T, rho):
