@@ -100,6 +100,44 @@ void orc_pure_derivatives(const double* params, const double* T, const double* r
     }
 }
 
+// the same in long double (cancellation-free site fractions), rounded to double on return: the exact values of the model
+void orc_pure_derivatives_ld(const double* params, const double* T, const double* rho, int64_t n, double* a,
+                             double* p, double* dp) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        typedef long double F;
+        PureParams<F> q = load_pure<F>(params + 8 * i);
+        F aa, pp, dd;
+        derivatives<F>(q, F(T[i]), F(rho[i]), aa, pp, dd);
+        a[i] = double(aa); p[i] = double(pp); dp[i] = double(dd);
+    }
+}
+
+// Exact gradient of L_i = ga a + gp p + gdp dp/drho (PcSaftPure.derivatives at one state point per row) with respect to every
+// input of the row: grad [n, 10] = dL_i/d(8 parameters, T, rho).  Nested duals: the Dual3 of `derivatives` over DualN<F, 10>,
+// every input seeded.  prec = 1: F = long double throughout, rounded to double only when the gradient is stored -- the referee.
+// prec = 0: the same code in double -- what an fp64 evaluation of the same formulas can deliver, the yardstick of the tests'
+// bars.  The mu column is exactly 0 where mu = 0 (mu enters squared); the association columns are exactly 0 where na = nb = 0
+// (rhoa = rhob = 0 multiply everything kappa_ab and epsilon_k_ab enter).
+void orc_pure_derivatives_vjp_exact(const double* params, const double* T, const double* rho, int64_t n, int prec,
+                                    const double* ga, const double* gp, const double* gdp, double* grad) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        auto run = [&](auto zero) {
+            typedef decltype(zero) F;
+            typedef DualN<F, 10> G;
+            G p[8];
+            for (int k = 0; k < 8; k++) p[k] = G::var(F(params[8 * i + k]), k);
+            PureParams<G> q = make_pure_params<G>(p);
+            G aa, pp, dd;
+            derivatives<G>(q, G::var(F(T[i]), 8), G::var(F(rho[i]), 9), aa, pp, dd);
+            for (int k = 0; k < 10; k++) grad[10 * i + k] = double(F(ga[i]) * aa.eps[k] + F(gp[i]) * pp.eps[k] + F(gdp[i]) * dd.eps[k]);
+        };
+        if (prec == 1) run((long double)0);
+        else run(double(0));
+    }
+}
+
 // plain Helmholtz energy density: feos_torch/pcsaft_pure.py:106-178
 void orc_pure_helmholtz(const double* params, const double* T, const double* rho, int64_t n, double* a) {
 #pragma omp parallel for schedule(static)
@@ -497,6 +535,38 @@ void orc_mix_derivatives_ld(const double* params, const double* kij, const doubl
         derivatives_mix<F>(q, F(T[i]), r, aa, pp, m2, v2);
         a[i] = double(aa); p[i] = double(pp);
         for (int k = 0; k < 2; k++) { mu[2 * i + k] = double(m2[k]); v[2 * i + k] = double(v2[k]); }
+    }
+}
+
+// Exact gradient of L_i = ga a + gp p + gmu . mu + gv . v (binary PcSaftMix.derivatives at one state point per row) with respect
+// to every input of the row: grad [n, 21] = dL_i/d(16 parameters [comp0 x 8, comp1 x 8], kij[0] = k_ij, kij[1] = eps_AiBj, T,
+// rho_0, rho_1).  Nested duals: the HyperDual<., 3> of derivatives_mix over DualN<F, 21>, every input seeded, safeguarded
+// association iterations (robust; their three closing Newton updates in dual arithmetic are the implicit differentiation).
+// prec = 1: F = long double throughout, rounded to double only when the gradient is stored -- the referee.  prec = 0: the same
+// code in double, the yardstick of the tests' bars.  `var` on eps_AiBj == 0 keeps the real part 0, so the mean combining rule
+// stays selected and that column is exactly 0; it is also 0 on every row that is not cross-associating (only that term reads it).
+void orc_mix_derivatives_vjp_exact(const double* params, const double* kij, const double* T, const double* rho, int64_t n,
+                                   int prec, const double* ga, const double* gp, const double* gmu, const double* gv,
+                                   double* grad) {
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t i = 0; i < n; i++) {
+        auto run = [&](auto zero) {
+            typedef decltype(zero) F;
+            typedef DualN<F, 21> G;
+            G p[16];
+            for (int k = 0; k < 16; k++) p[k] = G::var(F(params[16 * i + k]), k);
+            MixParams<G> q = make_mix_params<G>(p, G::var(F(kij[2 * i]), 16), G::var(F(kij[2 * i + 1]), 17));
+            q.robust = true;
+            G r[2] = {G::var(F(rho[2 * i]), 19), G::var(F(rho[2 * i + 1]), 20)}, aa, pp, m2[2], v2[2];
+            derivatives_mix<G>(q, G::var(F(T[i]), 18), r, aa, pp, m2, v2);
+            for (int k = 0; k < 21; k++) {
+                F e = F(ga[i]) * aa.eps[k] + F(gp[i]) * pp.eps[k];
+                for (int c = 0; c < 2; c++) e += F(gmu[2 * i + c]) * m2[c].eps[k] + F(gv[2 * i + c]) * v2[c].eps[k];
+                grad[21 * i + k] = double(e);
+            }
+        };
+        if (prec == 1) run((long double)0);
+        else run(double(0));
     }
 }
 

@@ -84,6 +84,8 @@ def lib():
         L.orc_num_threads.restype = _int
         L.orc_dual3_selftest.restype = _int
         L.orc_pure_derivatives.argtypes = [_f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p]
+        L.orc_pure_derivatives_ld.argtypes = [_f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p]
+        L.orc_pure_derivatives_vjp_exact.argtypes = [_f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p, _f64p, _f64p]
         L.orc_pure_helmholtz.argtypes = [_f64p, _f64p, _f64p, _i64, _f64p]
         L.orc_pure_vle.argtypes = [_f64p, _f64p, _i64, _int, _f64p, _f64p, _u8p, _i32p, _i32p]
         L.orc_pure_vapor_pressure.argtypes = [_f64p, _f64p, _i64, _int, _f64p, _u8p]
@@ -102,6 +104,7 @@ def lib():
         L.orc_mixn_derivatives_vjp_exact.argtypes = [_f64p, _f64p, _f64p, _int, _i64, _int, _f64p, _f64p, _f64p, _f64p, _f64p]
         L.orc_mixn_derivatives_vjp_exact.restype = _int
         L.orc_mix_derivatives_ld.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _f64p, _f64p, _f64p, _f64p]
+        L.orc_mix_derivatives_vjp_exact.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p, _f64p, _f64p, _f64p]
         L.orc_mix_bubble_dew_grad_ld.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _f64p, _f64p]
         L.orc_mix_bubble_dew_continuation.argtypes = [_f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _f64p, _f64p, _i32p, _i32p]
         _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
@@ -147,12 +150,27 @@ def _c(x, shape=None):
     return x
 
 
-def pure_derivatives(params, T, rho):
+def pure_derivatives(params, T, rho, prec=0):
+    """PcSaftPure.derivatives: a[n], p[n], dp/drho[n] (reduced).  prec=1: long double with the cancellation-free site fractions,
+    rounded to double on return -- the exact values of the model; prec=0: the fp64 restatement, unchanged."""
     params, T, rho = _c(params), _c(T), _c(rho)
     n = T.shape[0]
     a, p, dp = np.empty(n), np.empty(n), np.empty(n)
-    lib().orc_pure_derivatives(params, T, rho, n, a, p, dp)
+    (lib().orc_pure_derivatives_ld if prec == 1 else lib().orc_pure_derivatives)(params, T, rho, n, a, p, dp)
     return a, p, dp
+
+
+def pure_derivatives_vjp_exact(params, T, rho, ga, gp, gdp, prec=1):
+    """Gradient of L_i = ga_i a_i + gp_i p_i + gdp_i (dp/drho)_i (PcSaftPure.derivatives) by nested duals: grad [n, 10] =
+    dL_i/d(8 parameters, T, rho), every column seeded.  prec=1: long double throughout, rounded to double on return -- the
+    referee; prec=0: the same code in double, the yardstick for what fp64 can deliver."""
+    params, T, rho = _c(params), _c(T), _c(rho)
+    n = T.shape[0]
+    assert params.shape == (n, 8)
+    ga, gp, gdp = _c(ga, (n,)), _c(gp, (n,)), _c(gdp, (n,))
+    grad = np.empty((n, 10))
+    lib().orc_pure_derivatives_vjp_exact(params, T, rho, n, int(prec), ga, gp, gdp, grad)
+    return grad
 
 
 def pure_helmholtz(params, T, rho):
@@ -254,6 +272,20 @@ def mix_derivatives_exact(params, kij, T, rho):
     a, p, mu, v = np.empty(n), np.empty(n), np.empty((n, 2)), np.empty((n, 2))
     lib().orc_mix_derivatives_ld(params, kij, T, rho, n, a, p, mu, v)
     return a, p, mu, v
+
+
+def mix_derivatives_vjp_exact(params, kij, T, rho, ga, gp, gmu, gv, prec=1):
+    """Gradient of L_i = ga_i a_i + gp_i p_i + gmu_i . mu_i + gv_i . v_i (binary PcSaftMix.derivatives, safeguarded association)
+    by nested duals: grad [n, 21] = dL_i/d(16 parameters, kij[:, 0] = k_ij, kij[:, 1] = eps_AiBj, T, rho_0, rho_1), the column
+    order of pcs_mix_derivatives_vjp; every column seeded (eps_AiBj = 0 keeps the mean combining rule: that column is 0).
+    prec=1: long double throughout, rounded to double on return -- the referee; prec=0: the same code in double."""
+    params, kij, T, rho = _c(params), _c(kij), _c(T), _c(rho)
+    n = T.shape[0]
+    assert params.reshape(n, -1).shape == (n, 16) and kij.shape == (n, 2) and rho.shape == (n, 2)
+    ga, gp, gmu, gv = _c(ga, (n,)), _c(gp, (n,)), _c(gmu, (n, 2)), _c(gv, (n, 2))
+    grad = np.empty((n, 21))
+    lib().orc_mix_derivatives_vjp_exact(params, kij, T, rho, n, int(prec), ga, gp, gmu, gv, grad)
+    return grad
 
 
 def mixn_derivatives(params, T, rho, prec=0):

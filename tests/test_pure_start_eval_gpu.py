@@ -11,7 +11,7 @@ class-uniform).  Every class has rows with m < 2 and m > 2 (the dipole clamp), a
 nb = 0 next to eps_AB != 0 (na nb = 0: the association branch runs, its energy vanishes).
 
 Reference of the probe: a, p and a' from the oracle's long-double evaluation (mixn_derivatives with one component, prec=1);
-dp/drho from its fp64 evaluation (pure_derivatives: the only form in which the oracle hands it out; its rounding, ~1e-13, is
+dp/drho from its fp64 evaluation (pure_derivatives, written before that function had prec=1; its rounding, ~1e-13, is
 seven orders below the fp32 figures compared here).  The two evaluations are required to agree on a and p to 1e-10.  ceta
 from the oracle's formula in long double, rho = 0.5 / ceta rounded to double.
 
