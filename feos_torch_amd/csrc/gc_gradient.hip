@@ -683,9 +683,15 @@ extern "C" {
 // LDS of a workgroup: table + gradient accumulator + per thread: bond diameters 2*MAXE doubles, the dual model's diameters
 // 2*MAXE*(1+CHUNK) / the coefficient adjoints, the row bytes.  The kernel holds a full register file per wave and waits mostly
 // for its own stack frame, so the number of resident waves is what counts (measured: one wave per CU 6.6 ms, two 3.8 ms per 1e6
-// rows): 64-thread workgroups carry one copy of the table each and fit twice (S = 22: 59 KB); a 192-thread workgroup shares one
-// copy among three waves (S = 22: 149 KB; the VJP of `derivatives`, MODE 1, needs less per thread: four waves, 132 KB) -- the
-// largest workgroup that fits the CU's 160 KB is taken.
+// rows): a workgroup of several waves shares ONE copy of the table.  launch_gc_gradient_mode takes the largest of 256, 192 and
+// 64 threads whose request stays within the CU's 160 KB, and for the table sizes the ABI admits (S <= 32) that is one branch per
+// mode:
+//   MODE 0 (bubble / dew, 88 doubles per thread): 24 S^2 + 128 S + 704 BLOCK bytes.  256 threads need 180 224 B before the table
+//     and never fit; 192 threads fit for every S (S = 22: 149 KB; S = 32: 163 840 B, exactly the CU's LDS), so the tile is 192
+//     rows and the 64-thread branch (one table per wave, two workgroups per CU at S = 22) is never reached;
+//   MODE 1 (VJP of `derivatives`, 59 doubles per thread): 256 threads fit for every S (S = 32: 149 504 B), so neither the 192- nor
+//     the 64-thread branch is reached.
+// The unreachable branches are kept for a larger table limit.  (tests/test_gc_point_grad_gpu.py, tests/test_gc_state_gpu.py)
 static int launch_gc_gradient(int mode, const GcGradArgs& a, void* stream, const char* what) {
     return mode == 0 ? launch_gc_gradient_mode<0>(a, stream, what) : launch_gc_gradient_mode<1>(a, stream, what);
 }

@@ -874,4 +874,128 @@ int orc_gc_derivatives_vjp_exact(int S, const double* seg, const double* kab, co
     return bad;
 }
 
+// Exact gradient of the bubble / dew pressure p_i [Pa] of GcPcSaftMix.bubble_point / dew_point: the reference's final formula at
+// FIXED densities rho4 = (rhoV_1, rhoV_2, rhoL_1, rhoL_2) (feos_torch/gc_pcsaft.py:470-512), what torch reverse mode yields there.
+//   value    [n]    p_i
+//   grad_row [n,3]  dp_i/d(phi_0, phi_1, T), NOT weighted                  DualN<F, 4>, as orc_gc_bubble_dew_grad
+//   grad_kab [S,S]  sum_i w_i dp_i/d k_ab (symmetric pair, both entries)   the same duals, one pair of the row per pass
+//   grad_seg [S,8]  sum_i w_i dp_i/d segment table                         central differences of the long-double evaluation at
+//                   relative steps 1e-5 and 5e-6, Richardson-extrapolated (the table cannot be seeded: see
+//                   orc_gc_derivatives_vjp_exact, whose conventions for structurally-zero entries, epsilon_k = 0 and unused
+//                   segments hold here too).  NULL: the table part is skipped.
+//   seg_self_error [8]  per parameter column: largest |grad_seg - the same sum extrapolated from the steps 2e-5 and 1e-5| over the
+//                   largest |grad_seg| of the column -- the error of the differences, measured on these very rows and weights
+// prec = 1: F = long double, rounded to double only when a result is stored -- the referee.  prec = 0: the dual part (value,
+// grad_row, grad_kab) in double, the yardstick of the tests' bars; the table differences are long double either way.  The sums
+// over the rows are carried in long double.  A row of weight 0 is skipped entirely (value and grad_row 0), so that a call
+// masked to one model class costs that class only.
+int orc_gc_bubble_dew_vjp_exact(int S, const double* seg, const double* kab, const double* counts, const double* bonds,
+                                const double* phi, const double* T, const double* rho4, int64_t n, int dew, int prec,
+                                const double* w, double* value, double* grad_row, double* grad_kab, double* grad_seg,
+                                double* seg_self_error) {
+    typedef long double L;
+    int bad = 0;
+    const size_t nseg = (size_t)S * 8, nkab = (size_t)S * S;
+    std::vector<L> sum_seg(nseg, L(0)), sum_alt(nseg, L(0)), sum_kab(nkab, L(0));
+#pragma omp parallel reduction(| : bad)
+    {
+        std::vector<L> my_seg(nseg, L(0)), my_alt(nseg, L(0)), my_kab(nkab, L(0));
+        std::vector<double> tab(seg, seg + nseg);
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t i = 0; i < n; i++) {
+            value[i] = 0.0;
+            for (int k = 0; k < 3; k++) grad_row[3 * i + k] = 0.0;
+            if (w[i] == 0.0) continue;
+            GcRow r;
+            if (!gc_row(r, S, seg, kab, counts, bonds, phi, i)) { bad |= 1; continue; }
+            r.robust = true;
+            const L wi = w[i];
+            const double* c0 = r.counts;
+            const double* c1 = r.counts + S;
+            // ---- value, phi, T and k_ab: duals.  Directions: 0 = k_ab pair of the pass, 1, 2 = phi, 3 = T
+            auto duals = [&](auto zero) {
+                typedef decltype(zero) F;
+                typedef DualN<F, 4> G;
+                bool first = true;
+                auto pass = [&](int ka, int kb) {
+                    GcGradModel<G> model{r, G::var(F(kab[ka * S + kb]), 0), {G::var(F(phi[2 * i]), 1), G::var(F(phi[2 * i + 1]), 2)}, ka, kb};
+                    G Tg = G::var(F(T[i]), 3);
+                    G rv[2] = {G(F(rho4[4 * i])), G(F(rho4[4 * i + 1]))}, rl[2] = {G(F(rho4[4 * i + 2])), G(F(rho4[4 * i + 3]))};
+                    G pr = dew ? bubble_dew_formula_generic<G>(model, Tg, rv, rl) : bubble_dew_formula_generic<G>(model, Tg, rl, rv);
+                    G res = pr * Tg * F(P_UNIT);
+                    if (first) {
+                        value[i] = double(res.re);
+                        for (int k = 0; k < 3; k++) grad_row[3 * i + k] = double(res.eps[1 + k]);
+                        first = false;
+                    }
+                    return L(res.eps[0]);
+                };
+                for (int a = 0; a < S; a++)
+                    for (int b = 0; b <= a; b++) {
+                        if (!((c0[a] != 0.0 && c1[b] != 0.0) || (c0[b] != 0.0 && c1[a] != 0.0))) continue;
+                        const L g = wi * pass(a, b);
+                        my_kab[(size_t)a * S + b] += g;
+                        if (a != b) my_kab[(size_t)b * S + a] += g;
+                    }
+                if (first) pass(0, 0);  // a row without a segment pair (cannot happen: every molecule has a segment)
+            };
+            if (prec == 1) duals((long double)0);
+            else duals(double(0));
+            if (!grad_seg) continue;
+            // ---- segment table: Richardson-extrapolated central differences of the long-double evaluation
+            auto pressure = [&]() {
+                GcRow q;
+                gc_row(q, S, tab.data(), kab, counts, bonds, phi, i);
+                q.robust = true;
+                GcModel<L> model{q};
+                const L Ti = T[i];
+                L rv[2] = {L(rho4[4 * i]), L(rho4[4 * i + 1])}, rl[2] = {L(rho4[4 * i + 2]), L(rho4[4 * i + 3])};
+                L pr = dew ? bubble_dew_formula_generic<L>(model, Ti, rv, rl) : bubble_dew_formula_generic<L>(model, Ti, rl, rv);
+                return pr * Ti * L(P_UNIT);
+            };
+            for (int a = 0; a < S; a++) {
+                if (c0[a] == 0.0 && c1[a] == 0.0) continue;
+                for (int k = 0; k < 8; k++) {
+                    const double x = seg[8 * a + k];
+                    if (x == 0.0) continue;
+                    L d[3], h2[3];
+                    for (int lvl = 0; lvl < 3; lvl++) {
+                        const double h = (lvl == 0 ? 2e-5 : (lvl == 1 ? 1e-5 : 5e-6)) * std::fabs(x);
+                        volatile double xp = x + h, xm = x - h;  // the steps actually taken are xp - x and x - xm
+                        tab[8 * a + k] = xp;
+                        const L fp = pressure();
+                        tab[8 * a + k] = xm;
+                        const L fm = pressure();
+                        const L width = L(xp) - L(xm);
+                        d[lvl] = (fp - fm) / width;
+                        h2[lvl] = width * width;
+                    }
+                    tab[8 * a + k] = x;
+                    my_seg[(size_t)8 * a + k] += wi * ((h2[1] * d[2] - h2[2] * d[1]) / (h2[1] - h2[2]));
+                    my_alt[(size_t)8 * a + k] += wi * ((h2[0] * d[1] - h2[1] * d[0]) / (h2[0] - h2[1]));
+                }
+            }
+        }
+#pragma omp critical
+        {
+            for (size_t k = 0; k < nseg; k++) { sum_seg[k] += my_seg[k]; sum_alt[k] += my_alt[k]; }
+            for (size_t k = 0; k < nkab; k++) sum_kab[k] += my_kab[k];
+        }
+    }
+    for (size_t k = 0; k < nkab; k++) grad_kab[k] = double(sum_kab[k]);
+    if (grad_seg) {
+        for (size_t k = 0; k < nseg; k++) grad_seg[k] = double(sum_seg[k]);
+        for (int k = 0; k < 8; k++) {
+            L diff = 0, scale = 0;
+            for (int a = 0; a < S; a++) {
+                const L s = sum_seg[(size_t)8 * a + k], e = s - sum_alt[(size_t)8 * a + k];
+                if ((s < 0 ? -s : s) > scale) scale = s < 0 ? -s : s;
+                if ((e < 0 ? -e : e) > diff) diff = e < 0 ? -e : e;
+            }
+            seg_self_error[k] = scale > 0 ? double(diff / scale) : 0.0;
+        }
+    }
+    return bad;
+}
+
 }  // extern "C"

@@ -118,6 +118,9 @@ def lib():
         L.orc_gc_bubble_dew.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _f64p, _f64p, _u8p]
         L.orc_gc_bubble_dew.restype = _int
         L.orc_gc_bubble_dew_grad.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _int, _int, _f64p, _f64p]
+        L.orc_gc_bubble_dew_vjp_exact.argtypes = [_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64, _int, _int, _f64p, _f64p, _f64p,
+                                                  _f64p, ctypes.c_void_p, ctypes.c_void_p]  # grad_seg, seg_self_error: may be NULL
+        L.orc_gc_bubble_dew_vjp_exact.restype = _int
         _lib = L
     return _lib
 
@@ -464,6 +467,37 @@ def gc_bubble_dew_grad(enc, phi, T, rho4, dew, s1, s2, exact=False):
     lib().orc_gc_bubble_dew_grad(enc["S"], _c(enc["seg"]), _c(enc["kab"]), _c(enc["counts"]), _c(enc["bonds"]), phi, T, rho4,
                                  n, int(bool(dew)), ka, kb, int(bool(exact)), val, grad)
     return val, grad
+
+
+def gc_bubble_dew_vjp_exact(enc, phi, T, rho4, dew, weights=None, prec=1, segments=True):
+    """The bubble / dew pressure of GcPcSaftMix.bubble_point / dew_point (the reference's final formula at FIXED densities rho4,
+    feos_torch/gc_pcsaft.py:470-512) and its exact gradient, evaluated in long double and rounded to double only on return:
+      value          [n]    p_i [Pa],
+      grad_row       [n,3]  dp_i/d(phi_0, phi_1, T), not weighted,
+      grad_kab       [S,S]  sum_i w_i dp_i/d k_ab; an entry is the derivative w.r.t. the symmetric pair and is stored at both
+                            places; one pass per pair the row's segments can form,
+      grad_seg       [S,8]  sum_i w_i dp_i/d segment table: central differences of the long-double evaluation at relative steps
+                            1e-5 and 5e-6, Richardson-extrapolated, only the segments a row uses are perturbed; the conventions
+                            of gc_derivatives_vjp_exact (structurally-zero entries, epsilon_k = 0, unused segments: 0),
+      seg_self_error [8]    per column, largest |grad_seg - the same sum extrapolated from the steps 2e-5 and 1e-5| relative to
+                            the column's largest entry: the referee's own error on the table, measured on these rows and weights.
+    weights None = 1.  A row of weight 0 is skipped entirely (its value and grad_row are 0): a call masked to one model class
+    costs that class only.  prec=0 runs the dual part (value, grad_row, grad_kab) in fp64 -- what an fp64 evaluation of the same
+    formulas can deliver, the yardstick of the tests' bars.  segments=False skips the table differences (grad_seg and
+    seg_self_error are None)."""
+    phi, T, rho4 = _c(phi), _c(T), _c(rho4)
+    n = T.shape[0]
+    assert phi.shape == (n, 2) and rho4.shape == (n, 4)
+    w = np.ones(n) if weights is None else _c(weights, (n,))
+    S = enc["S"]
+    val, grow, gkab = np.zeros(n), np.zeros((n, 3)), np.zeros((S, S))
+    gseg, err = (np.zeros((S, 8)), np.zeros(8)) if segments else (None, None)
+    bad = lib().orc_gc_bubble_dew_vjp_exact(S, _c(enc["seg"]), _c(enc["kab"]), _c(enc["counts"]), _c(enc["bonds"]), phi, T, rho4, n,
+                                            int(bool(dew)), int(prec), w, val, grow, gkab,
+                                            gseg.ctypes.data if segments else None, err.ctypes.data if segments else None)
+    if bad:
+        raise Exception("Only up to one associating segment per component is allowed!")
+    return val, grow, gkab, gseg, err
 
 
 def gc_segment_grad_fd(enc, phi, T, rho4, dew, weights=None, rel=1e-6):

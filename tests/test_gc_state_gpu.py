@@ -320,8 +320,9 @@ def test_table_size_selects_the_block_but_not_the_result(amd, table, big):
     accumulator), and the largest BLOCK of 256, 192, 64 that stays within 160 KB is taken:
       S =  6: 122 464 B -> BLOCK 256;   S = 23: 138 416 B -> BLOCK 256;   S = 32: 149 504 B -> BLOCK 256.
     S = 32 is the largest table the ABI admits, so the VJP runs at BLOCK = 256 for EVERY table: its 192- and 64-thread
-    branches cannot be reached (they serve the bubble / dew gradient, MODE 0, which needs 88 doubles per thread), and no choice
-    of S makes two different block sizes run.  What the three tables do change is the LDS layout (table stride S, offset of the
+    branches cannot be reached, and no choice of S makes two different block sizes run.  (The bubble / dew gradient, MODE 0,
+    needs 88 doubles per thread: there BLOCK = 256 never fits and BLOCK = 192 always does -- exactly 160 KB at S = 32 -- so the
+    64-thread branch serves neither mode; tests/test_gc_point_grad_gpu.py.)  What the three tables do change is the LDS layout (table stride S, offset of the
     accumulator, of the bond area and of the rows) and the segment indices.
 
     Forward outputs, jac9 and agg agree across the tables to 1e-12 relative (measured: bit-identical), the grad_seg rows of the

@@ -9,6 +9,7 @@ The long-double referee of the state functions (gc_derivatives(prec=1), gc_deriv
 fixtures and to the reference's own autograd (tests/golden/deriv_grad.json) before any kernel is judged by it
 (tests/test_gc_state_gpu.py)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -158,3 +159,138 @@ def test_exact_vjp_matches_reference_autograd_reference_pairs(oracle, table):
     assert np.max(np.abs(leaf - np.array(g["grad_kab"]))) < VJP_TOL * np.max(np.abs(g["grad_kab"]))
     _rows_close(grow[:, 2:3], np.array(g["grad_T"])[:, None], 1e-8)
     _rows_close(grow[:, 3:5], g["grad_rho"], 1e-8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the referee of the bubble / dew gradient (gc_bubble_dew_vjp_exact), tied down before tests/test_gc_point_grad_gpu.py
+# judges pcs_gc_jacobian and pcs_gc_segment_gradient by it
+# ---------------------------------------------------------------------------------------------------------------------------
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import gc_point_rows as gp  # noqa: E402
+
+MODES = [("bubble", False), ("dew", True)]
+SEGGRAD_KEYS = [("bubble", False), ("dew", True), ("bubble_butane_propane", False), ("dew_butane_propane", True),
+                ("bubble_full_table", False), ("dew_full_table", True)]
+
+
+def _seg_bar(self_error):
+    return np.maximum(gp.FLOOR, 10.0 * self_error)
+
+
+@pytest.mark.parametrize("name,dew", MODES)
+def test_point_referee_equals_the_seeded_pair_gradient(oracle, name, dew):
+    """value, dp/d(phi, T) per row and the weighted k_ab sums of gc_bubble_dew_vjp_exact against gc_bubble_dew_grad(exact=True),
+    which seeds one k_ab pair per call, for each of the four binary records on the ~720 rows of tests/tools/gc_point_rows.py: to
+    1e-15 relative (the same duals; only the weighted sum, carried in long double here, differs).  prec=0 likewise against
+    exact=False.  A k_ab pair no row can form has gradient exactly 0."""
+    r = gp.solved(oracle, dew)
+    ref = gp.referee(oracle, dew)["all"]
+    enc, w = r["enc"], r["w"]
+    ident = enc["ident"]
+    assert np.array_equal(ref["grad_kab"], ref["grad_kab"].T) and np.array_equal(ref["kab64"], ref["kab64"].T)
+    for prec, gk, grow in ((1, ref["grad_kab"], ref["grad_row"]), (0, ref["kab64"], ref["row64"])):
+        for s1, s2, _ in r["kab_list"]:
+            val, grad = oracle.gc_bubble_dew_grad(enc, r["phi"], r["T"], r["rho4"], dew, s1, s2, exact=bool(prec))
+            if prec == 1:
+                assert np.max(np.abs(ref["value"] / val - 1.0)) < 1e-15
+            # (a call that seeds another pair than the referee's first pass forms that pair's 1 - k_ab in F, not in double)
+            err = gp.row_error(grow, grad[:, 1:4])
+            assert max(err["phi"].max(), err["T"].max()) < 1e-15, (prec, s1, s2, err["phi"].max(), err["T"].max())
+            terms = grad[:, 0].astype(np.longdouble) * w.astype(np.longdouble)
+            want = terms.sum()
+            got = gk[ident.index(s1), ident.index(s2)]
+            assert want != 0 and abs(np.longdouble(got) - want) < 1e-15 * np.abs(terms).sum(), (prec, s1, s2, got, float(want))
+    unreachable = ident.index("C≡CH")  # no molecule of the library carries it
+    assert np.all(ref["grad_kab"][unreachable] == 0.0) and np.all(ref["grad_seg"][unreachable] == 0.0)
+
+
+@pytest.mark.parametrize("key,dew", SEGGRAD_KEYS)
+def test_point_referee_matches_reference_autograd(oracle, table, key, dew):
+    """grad_seg of gc_bubble_dew_vjp_exact against the reference's own torch autograd through its bubble / dew tail (the six
+    fixtures of tests/golden/gc_seggrad.json): all eight columns on the table without '>C<', the seven finite ones on the full
+    table (epsilon_k is NaN there in the reference).  Compared where the referee reports an entry -- the reference also
+    differentiates through the zero-valued kappa_ab, epsilon_k_ab, na, nb of the site-less segments of an associating molecule,
+    which the referee's differences leave alone -- at the referee's own bar max(1e-10, 10 seg_self_error) of the column scale.
+    Measured: at most 2.4e-10 (sigma, dew_butane_propane) against a bar of 2.5e-9; value to 3.5e-14 relative."""
+    g = load_golden("gc_seggrad.json")
+    full = key.endswith("full_table")
+    tab = table if full else [(s, v) for s, v in table if s in g["table_without_C"]]
+    g = g[key]
+    enc = oracle.gc_encode(tab, g["segment_lists"], g["bond_lists"], [tuple(k) for k in g["kab_list"]])
+    phi, T = np.array(g["phi"]), np.array(g["T"])
+    _, rho4, st = oracle.gc_bubble_dew(enc, phi, T, np.array(g["z"]), np.array(g["p_init"]), dew, prec=1)
+    assert not st.any()
+    val, _, _, gseg, self_error = oracle.gc_bubble_dew_vjp_exact(enc, phi, T, rho4, dew, np.array(g["weights"]))
+    assert np.max(np.abs(val / np.array(g["value"]) - 1.0)) < 1e-12
+    ref = np.array(g["grad_segments"], dtype=float)  # [8][S]
+    used = enc["counts"].sum(axis=(0, 1)) > 0
+    cols = [0, 1, 3, 4, 5, 6, 7] if full else list(range(8))
+    assert np.all(np.isnan(ref[2])) if full else np.all(np.isfinite(ref))
+    assert np.all(self_error < 1e-8), self_error
+    print(f"\n   {key}: seg_self_error {self_error}")
+    for k in cols:
+        mask = used & (enc["seg"][:, k] != 0.0)
+        assert np.all(gseg[~mask, k] == 0.0)
+        scale = np.max(np.abs(ref[k]))
+        if not mask.any():
+            continue
+        err = np.max(np.abs(gseg[mask, k] - ref[k][mask])) / scale
+        print(f"   column {k}: {err:.2e} (bar {_seg_bar(self_error)[k]:.2e})")
+        assert err <= _seg_bar(self_error)[k], (k, err)
+
+
+@pytest.mark.parametrize("key,dew", [("bubble_full_table", False), ("dew_full_table", True)])
+def test_point_referee_matches_finite_differences(oracle, table, key, dew):
+    """grad_seg against gc_segment_grad_fd (fp64 central differences at one step, the yardstick of
+    tests/test_gc_seggrad_gpu.py) on the full-table fixtures, epsilon_k included: at 2e-6 of the column scale, the accuracy at which
+    that test relies on the function for these fixtures.  Measured: at most 4.4e-8 (na, bubble)."""
+    g = load_golden("gc_seggrad.json")[key]
+    enc = oracle.gc_encode(table, g["segment_lists"], g["bond_lists"], [tuple(k) for k in g["kab_list"]])
+    phi, T, w = np.array(g["phi"]), np.array(g["T"]), np.array(g["weights"])
+    _, rho4, st = oracle.gc_bubble_dew(enc, phi, T, np.array(g["z"]), np.array(g["p_init"]), dew, prec=1)
+    assert not st.any()
+    gseg = oracle.gc_bubble_dew_vjp_exact(enc, phi, T, rho4, dew, w)[3]
+    fd = oracle.gc_segment_grad_fd(enc, phi, T, rho4, dew, weights=w)
+    assert np.array_equal(gseg != 0.0, fd != 0.0)  # the same entries are reported
+    for k in range(8):
+        scale = np.max(np.abs(gseg[:, k]))
+        assert scale > 0 and np.max(np.abs(gseg[:, k] - fd[:, k])) / scale < 2e-6, k
+
+
+@pytest.mark.parametrize("name,dew", MODES)
+def test_point_referee_is_linear_in_the_weights(oracle, name, dew):
+    """The sums of gc_bubble_dew_vjp_exact are linear in the weights, and the calls masked to one model class add up to the call
+    on the whole set: grad_seg to 1e-15 of the column scale, the k_ab records to 1e-15 of the largest (long-double sums, rounded
+    once).  value and grad_row do not depend on the weights; a row of weight 0 is skipped (its value and grad_row are 0).
+    seg_self_error of every class and of the whole set is printed and is below 1e-8 (measured: at most 1.8e-10)."""
+    r = gp.solved(oracle, dew)
+    ref = gp.referee(oracle, dew)
+    whole = ref["all"]
+    col = np.max(np.abs(whole["grad_seg"]), axis=0)
+    kscale = np.max(np.abs(gp.kab_records(r, whole["grad_kab"])))
+    assert np.all(col > 0) and kscale > 0
+    sum_seg, sum_kab = np.zeros_like(whole["grad_seg"]), np.zeros_like(whole["grad_kab"])
+    print()
+    for cname, v in ref.items():
+        print(f"   {name:6s} {cname:15s} seg_self_error " + " ".join(f"{e:.1e}" for e in v["seg_self_error"]))
+        assert np.all(v["seg_self_error"] < 1e-8), (cname, v["seg_self_error"])
+        if cname == "all":
+            continue
+        mask = r["cls"] == {n: c for c, n in gp.CLASS_NAMES.items()}[cname]
+        assert np.array_equal(v["value"][mask], whole["value"][mask]) and np.all(v["value"][~mask] == 0.0)
+        assert np.array_equal(v["grad_row"][mask], whole["grad_row"][mask]) and np.all(v["grad_row"][~mask] == 0.0)
+        sum_seg += v["grad_seg"]
+        sum_kab += v["grad_kab"]
+    assert np.max(np.abs(sum_seg - whole["grad_seg"]) / col) < 1e-15
+    assert np.max(np.abs(sum_kab - whole["grad_kab"])) < 1e-15 * kscale
+    # linearity on the first 100 rows: f(w1 + 2 w2) = f(w1) + 2 f(w2)
+    sl = slice(0, 100)
+    enc = dict(r["enc"], counts=r["enc"]["counts"][sl], bonds=r["enc"]["bonds"][sl])
+    rng = np.random.default_rng(3)
+    w1, w2 = rng.uniform(0.5, 1.5, 100), rng.uniform(-1.0, 1.0, 100)
+    f = lambda w: oracle.gc_bubble_dew_vjp_exact(enc, r["phi"][sl], r["T"][sl], r["rho4"][sl], dew, w)
+    a, b, c = f(w1), f(w2), f(w1 + 2.0 * w2)
+    assert np.array_equal(a[0], c[0]) and np.array_equal(a[1], c[1])
+    scale = np.max(np.abs(a[3]), axis=0)
+    assert np.max(np.abs(a[3] + 2.0 * b[3] - c[3]) / scale) < 1e-14
+    assert np.max(np.abs(a[2] + 2.0 * b[2] - c[2])) < 1e-14 * np.max(np.abs(a[2]))
