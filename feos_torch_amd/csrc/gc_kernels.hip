@@ -27,38 +27,7 @@ constexpr int GJBLOCK = 256;
 // fast-pass caps (mix_solver.hpp).  A/B on the synthetic dew batch (scripts/dev/ab_gc.py): 12/12: 9.0 ms, 6/8: 7.9, 4/8: 8.4, 7/7: 8.6
 constexpr int GC_FAST_SS = 6, GC_FAST_NEWTON = 8;
 constexpr int GC_RETRY_BLOCKS = 1024;
-// no-progress leash of the dew-point Newton here (mixture kernels: 20, followed by their damped run): the second pass ends with its
-// slowest row; 10 loses no row of the synthetic batch and shortens it: dew 3.70 -> 3.60 ms per 1e6 rows
-constexpr int GC_NO_PROGRESS_DEW = 10;
-
-// association class x polarity of a row (the evaluation's branches): key of the workgroup bucketing in the fast pass
-constexpr int GC_BINS = 8;
-__device__ __forceinline__ int gc_bucket(const unsigned char* __restrict__ row, const GcTable& tb) {
-    int associating = 0, self_assoc = 0, polar = 0;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        double ka = 0.0, eab = 0.0, na = 0.0, nb = 0.0, mu2 = 0.0;
-#pragma unroll 1
-        for (int e = 0; e < GC_MAXE; e++) {
-            const int n = row[16 + i * GC_MAXE + e];
-            if (n == 0) continue;
-            const double* p = tb.seg + 8 * row[i * GC_MAXE + e];
-            mu2 += n * p[3] * p[3];
-            ka += n * p[4];
-            eab += n * p[5];
-            na += n * p[6];
-            nb += n * p[7];
-        }
-        associating += (ka * eab != 0.0);
-        self_assoc += (na * nb != 0.0);
-        polar |= (mu2 > 0.0);
-    }
-    int cls = 0;
-    if (associating == 1 && self_assoc == 1) cls = 1;
-    if (associating == 2 && self_assoc == 1) cls = 2;
-    if (associating == 2 && self_assoc == 2) cls = 3;
-    return 2 * cls + polar;
-}
+// (GC_NO_PROGRESS_DEW, GC_BINS and gc_bucket: gc_kernel_common.hpp, shared with gc_temperature.hip)
 
 // (A work-queue schedule as in mix_kernels.hip was measured here too: the gc rows need nearly the same number of
 // evaluations each, so it only adds the refill overhead: bubble 4.1 -> 4.7 ms, dew 12.4 -> 15.3 ms per 1e6 rows.)

@@ -57,12 +57,16 @@ struct MixTempResult {
     int iters;    // trials (outer iterations)
 };
 
-// m: the caller's model struct (coefficients in m.c; left at an unspecified temperature).  fail: the row is bad -- the lane
-// then carries a harmless row of the caller's through the wave-uniform code and takes no part in any solve.
-// Returns 0 (solved) or 1.
-template <bool DEW, class Model>
-PCS_DEV int mix_temperature(Model& m, const double* par, double k0, double k1, double z, double p_spec, double t_init, bool fail,
-                            MixTempResult& out) {
+// The outer iteration, shared by the binary-mixture and the gc kernels (mix_temperature below, gc_temperature.hpp); the two
+// differ in how the model is set to a temperature and in the cold solve of a trial, which come in as callables:
+//   set_temperature(T)                                  the coefficients of m at T
+//   trial(T, on, warm, rs, ri0, ri1, r) -> solved       one bubble / dew solve at the model's temperature on the lanes with `on`
+//                                                       (wave-uniform call), warm-started from (rs, ri0, ri1) where `warm`
+// m: the caller's model struct (left at an unspecified temperature).  fail: the row is bad -- the lane then carries a harmless
+// row of the caller's through the wave-uniform code and takes no part in any solve.  Returns 0 (solved) or 1.
+template <class Model, class SetT, class Trial>
+PCS_DEV int bubble_dew_temperature_loop(Model& m, double p_spec, double t_init, bool fail, MixTempResult& out, SetT set_temperature,
+                                        Trial trial) {
     out.T = 0.0;
     out.r.spec0 = out.r.spec1 = out.r.inc0 = out.r.inc1 = out.r.p = 0.0;
     out.r.iters = 0;
@@ -78,15 +82,15 @@ PCS_DEV int mix_temperature(Model& m, const double* par, double k0, double k1, d
         const bool on = !fail && !done;
         const double T = 1.0 / x;
         const bool use_warm = warm && !confirm && !cold_only;
-        mix_coef<double>(m.c, par, k0, k1, T);
+        set_temperature(T);
         MixResult r;
         r.spec0 = r.spec1 = r.inc0 = r.inc1 = r.p = 0.0;
         r.iters = 0;
-        const bool ok = bubble_dew_trial_sm<DEW>(m, z, p_spec / (T * P_UNIT), on, use_warm, rs, ri0, ri1, r) == BD_OK;
+        const bool ok = trial(T, on, use_warm, rs, ri0, ri1, r);
         double s = 0.0;  // d ln p / dT
         if (__ballot(ok) != 0ull) {
             const double T2 = T * (1.0 + MIXT_TANGENT_H);
-            mix_coef<double>(m.c, par, k0, k1, T2);
+            set_temperature(T2);
             if (ok) {
                 const PhaseEval es = phase_eval(m, r.spec0, r.spec1);
                 const PhaseEval en = phase_eval(m, r.inc0, r.inc1);
@@ -161,6 +165,17 @@ PCS_DEV int mix_temperature(Model& m, const double* par, double k0, double k1, d
         if (__ballot(!fail && !done) == 0ull) break;
     }
     return (done && !fail) ? 0 : 1;
+}
+
+// Binary mixture: mix_coef at T, a trial is bubble_dew_trial_sm (mix_solver_sm.hpp).  m.c is filled from (par, k0, k1).
+template <bool DEW, class Model>
+PCS_DEV int mix_temperature(Model& m, const double* par, double k0, double k1, double z, double p_spec, double t_init, bool fail,
+                            MixTempResult& out) {
+    return bubble_dew_temperature_loop(
+        m, p_spec, t_init, fail, out, [=, &m](double T) { mix_coef<double>(m.c, par, k0, k1, T); },
+        [=, &m](double T, bool on, bool warm, double rs, double ri0, double ri1, MixResult& r) {
+            return bubble_dew_trial_sm<DEW>(m, z, p_spec / (T * P_UNIT), on, warm, rs, ri0, ri1, r) == BD_OK;
+        });
 }
 
 }  // namespace pcs

@@ -247,6 +247,74 @@ class _GcBubbleDew(torch.autograd.Function):
         return (None, None, gk, gphi, gT, None, None, None, *gseg)
 
 
+class _GcBubbleDewTemperature(torch.autograd.Function):
+    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for the solve
+    (csrc/gc_temperature.hip), then as _GcBubbleDew: one compaction plan, gathers only when rows were dropped.  Gradient by the
+    implicit-function theorem on p(theta, T) = p_spec: with J_T = dp/dT (column 6 of pcs_gc_jacobian at the solved state) an
+    upstream gradient g of T is the upstream gradient g' = -g / J_T of the pressure for k_ab, phi and the segment table --
+    the pressure's own backward kernels, no new one -- and dT/dp_spec = 1 / J_T."""
+
+    @staticmethod
+    def forward(ctx, dew, model, kab, phi, pressure, molefracs, temperature, check, *segment_parameters):
+        dev, S = model.device, model.S
+        table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
+        ph = native._prep(phi, dev, (2,))
+        r = native.gc_bubble_dew_temperature(table, S, model.rows, ph, native._prep(pressure, dev), native._prep(molefracs, dev),
+                                             native._prep(temperature, dev), dew, order=model._class_order(table))
+        comp = native.Compaction(r["status"])
+        value = comp.gather(r["t"])
+        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, pressure
+        ctx.seg_needs = list(ctx.needs_input_grad[8:])
+        # the class order belongs to the uncompacted rows: used when every row converged
+        order = model._class_order(table) if comp.all_ok else None
+        ctx.comp = None
+        if any(ctx.needs) or any(ctx.seg_needs):
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": value}
+            rho4_ok = comp.gather(r["rho4"])
+            # dp/dT is needed whatever the gradient goes to
+            keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], value, rho4_ok, dew, order=order)
+            if any(ctx.seg_needs):  # the segment gradient runs in backward, at the densities
+                keep["rho4"] = rho4_ok
+                if order is not None:
+                    keep["order"] = order
+            ctx.kept = tuple(keep)  # what was saved, by name
+            ctx.save_for_backward(*keep.values())
+            ctx.comp = comp
+        ctx.dew, ctx.S = bool(dew), S
+        ctx.seg_devs = [p.device for p in segment_parameters]
+        ctx.devs = (kab.device, phi.device, pressure.device)
+        flags = ()
+        if check:
+            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.gc_stability(
+                table, S, comp.gather(model.rows), comp.gather(ph), value, feed, order=order)),)
+        return (*_shell.finish(ctx, phi.device, [value], r["status"], *flags), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, *_g_flags):
+        nseg = len(ctx.seg_needs)
+        comp, S = ctx.comp, ctx.S
+        if comp is None:  # nothing the temperature depends on required a gradient
+            return (None,) * (8 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T, jac = kept["table"], kept["rows"], kept["ph"], kept["T"], kept["jac"]
+        g = g_value.to(table.device).contiguous()
+        inv = 1.0 / jac[:, 6]
+        gp = -g * inv  # upstream gradient of the pressure along p(theta, T) = p_spec
+        gk = gphi = gpres = None
+        if ctx.needs[0]:
+            gk = _kab_gradient(table, S, rows, ph, T, gp * jac[:, 1], gp * jac[:, 4]).to(ctx.devs[0])
+        if ctx.needs[1]:
+            gphi = comp.expand(_phi_gradient(jac, kept["agg"], ph), gp).to(ctx.devs[1])
+        if ctx.needs[2]:
+            gpres = comp.expand(inv, g).view(comp.n).to(ctx.devs[2])
+        gseg = [None] * nseg
+        if any(ctx.seg_needs):
+            G = native.gc_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout=gp, order=kept.get("order"))
+            gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
+        return (None, None, gk, gphi, gpres, None, None, None, *gseg)
+
+
 class GcPcSaftMix(_shell.Reducible):
     def __init__(self, segment_identifier, parameter, segment_lists, bond_lists, binary_segment_records, phi=None):
         """Arguments as the reference (feos_torch/gc_pcsaft.py:14-22): segment identifiers [S], the
@@ -306,6 +374,32 @@ class GcPcSaftMix(_shell.Reducible):
         # mole fractions and initial pressure do not enter the reference's final formula (:483-490): no gradient flows to them
         *out, comp = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure),
                                         bool(check_stability), *self._segment_parameters)
+        self._reduce(comp)
+        return tuple(out)
+
+    def bubble_temperature(self, pressure, liquid_molefracs, temperature, check_stability=False):
+        """(T [K], nans): the temperature at which the liquid of mole fraction `liquid_molefracs` (component 1) starts to boil
+        at `pressure` [Pa], i.e. bubble_point(T, x, .) = pressure, solved in one kernel (csrc/gc_temperature.hpp) from the
+        mandatory first iterate `temperature` [K].  Values for the converged rows only, the model is reduced like bubble_point
+        does.  Differentiable w.r.t. the eight segment parameter vectors, k_ab, phi and pressure (implicit-function theorem on
+        the pressure's gradients: dT/dp = 1 / (dp/dT)); mole fractions and first iterate receive no gradient.  A row fails
+        where no trial temperature near the first iterate has an equilibrium, where the pressure lies above the bubble line,
+        or on a branch on which the pressure falls with the temperature (include/pcsaft_hip.h, pcs_gc_bubble_dew_temperature).
+        check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class."""
+        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability)
+
+    def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False):
+        """(T [K], nans): the temperature at which the vapour of mole fraction `vapor_molefracs` starts to condense at
+        `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
+        such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution."""
+        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability)
+
+    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False):
+        # the mole fractions do not enter the reference's final formula and the first iterate only starts the search: no
+        # gradient flows to either
+        *out, comp = _GcBubbleDewTemperature.apply(dew, self, self.kab, self.phi, torch.as_tensor(pressure, dtype=torch.float64),
+                                                   _detached(molefracs), _detached(temperature), bool(check_stability),
+                                                   *self._segment_parameters)
         self._reduce(comp)
         return tuple(out)
 

@@ -646,6 +646,31 @@ def gc_bubble_dew(table, S, rows, phi, temperature, molefracs, pressure, dew, wa
     return {"p": p, "rho4": rho4, "status": status.view(torch.bool), "iters": iters}
 
 
+def gc_bubble_dew_temperature(table, S, rows, phi, pressure, molefracs, temperature, dew, want_iters=False, order=None):
+    """Bubble (dew=False) / dew (dew=True) temperatures of gc rows at `pressure` [Pa] from the first iterate `temperature` [K]
+    (pcs_gc_bubble_dew_temperature).  table / rows / order as for gc_bubble_dew (order None: rows bucketed by class inside
+    each workgroup, same results).
+    -> dict(t [K], rho4 [n,4] A^-3 = (rhoV_1, rhoV_2, rhoL_1, rhoL_2) at t, status bool (True = failed)[, iters int32])."""
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    pressure = _prep(pressure, device)
+    molefracs = _prep(molefracs, device)
+    temperature = _prep(temperature, device)
+    n = pressure.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi, molefracs=molefracs, temperature=temperature)
+    _check_order(order, n, device)
+    t, rho4 = _news(device, n, (n, 4))
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if want_iters else None
+    _call(device, "pcs_gc_bubble_dew_temperature", int(bool(dew)), table, int(S), rows, phi, pressure, molefracs, temperature, n,
+          t, rho4, status, iters, order)
+    out = {"t": t, "rho4": rho4, "status": status.view(torch.bool)}
+    if want_iters:
+        out["iters"] = iters
+    return out
+
+
 def gc_derivatives(table, S, rows, phi, temperature, density):
     device = table.device
     phi = _prep(phi, device, (2,))

@@ -398,6 +398,40 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
                       const double* z, const double* p_init, int64_t n, double* p_out, double* rho4, uint8_t* status,
                       int32_t* iters, const int32_t* order, void* workspace, void* stream);
 
+/*
+ * gc-PC-SAFT bubble (dew = 0) / dew (dew = 1) TEMPERATURE at a given pressure (ABI 112): the T with p_bubble(T, z) = p_spec
+ * (resp. p_dew), the inverse of pcs_gc_bubble_dew in its temperature argument, with the partial densities of both phases at
+ * that T.  The outer iteration is that of pcs_mix_bubble_dew_temperature (csrc/mix_temperature.hpp, one code for both):
+ * safeguarded Newton on f = ln p(T) - ln p_spec in 1/T, slope from a temperature tangent at fixed densities, trials
+ * warm-started from the last solved one, an accepted warm trial confirmed by a cold one.  A cold trial is the solve of
+ * pcs_gc_bubble_dew without a work list at the trial temperature with the initial pressure p_spec (csrc/gc_temperature.hpp),
+ * so pcs_gc_bubble_dew at t_out answers p_spec.  The reference has no counterpart.
+ *   table, S, rows, phi  in   as for pcs_gc_bubble_dew (rows 16-byte aligned)
+ *   p_spec  [n]     in   Pa, the specified pressure
+ *   z       [n]     in   mole fraction of component 1 in the specified phase (liquid for bubble, vapour for dew), 0 < z < 1
+ *   t_init  [n]     in   K, the first iterate (mandatory)
+ *   t_out   [n]     out  K     (optional)
+ *   rho4    [n,4]   out  A^-3 (rhoV_1, rhoV_2, rhoL_1, rhoL_2) at t_out: what pcs_gc_jacobian and pcs_gc_segment_gradient
+ *                        need (optional, 16-byte aligned)
+ *   status  [n]     out  uint8, 0 = solved, 1 = failed; a failed row has t_out = 0, rho4 = 0, iters = -1.  A row fails AT ONCE
+ *                        when p_spec or t_init is non-finite or <= 0, z is non-finite or outside 0 < z < 1, or phi is
+ *                        non-finite; otherwise when: no trial finds an equilibrium at t_init nor at 8 temperatures below it
+ *                        (each lower by a factor 1.1); p_spec lies above the highest pressure of the line (the bracket between
+ *                        a solved trial and one without an equilibrium closes to 1e-6); a solved trial has a slope
+ *                        d ln p / dT that is not positive and finite -- the retrograde dew branch near a mixture critical
+ *                        point is not served --; or after 40 trials.
+ *                        Accepted: |ln p(T) - ln p_spec| <= 1e-12, or <= 1e-11 directly after a trial within 1e-8.
+ *   iters   [n]     out  int32 trial temperatures used, -1 for failed rows (optional, diagnostics)
+ *   order   [n]     in   optional class order of the rows as for pcs_gc_bubble_dew (NULL: bucketed by class inside each
+ *                        workgroup); only the schedule changes, results are identical.  One row per lane, no work queue.
+ * A row's result does not depend on the rows it shares a wave with.  Backward pass: J = pcs_gc_jacobian at (t_out, rho4),
+ * implicit-function theorem on p(theta, T) = p_spec: every gradient of the pressure times -1 / J[:, 6], dT/dp_spec = 1 / J[:, 6]
+ * (pcs_gc_segment_gradient with gout = -g / J[:, 6] for the segment table).
+ */
+int pcs_gc_bubble_dew_temperature(int dew, const double* table, int S, const uint8_t* rows, const double* phi,
+                                  const double* p_spec, const double* z, const double* t_init, int64_t n, double* t_out,
+                                  double* rho4, uint8_t* status, int32_t* iters, const int32_t* order, void* stream);
+
 /* GcPcSaftMix.derivatives (feos_torch/gc_pcsaft.py:443-468): a, p, mu [n,2], v [n,2] at rho [n,2]. */
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream);

@@ -17,6 +17,9 @@ with HIP events on the launch stream, inputs resident in HBM.
   mix_incipient: the backward kernels of bubble_point / dew_point on the converged rows of config 4: pcs_mix_jacobian (pressure
             gradient, the default) next to pcs_mix_point_jacobian with the pressure block only, the composition block only and
             both (incipient_molefracs=True); the fused call has to cost less than two pcs_mix_jacobian launches
+  gc_temperature: GcPcSaftMix.bubble_temperature / dew_temperature kernel (pcs_gc_bubble_dew_temperature), batch 1e6 minus the
+            rows bubble_point / dew_point fail on, at the pressures those give at the batch temperatures, started 5 % below
+            the answer; bubble_point / dew_point alongside, trial histogram and failed rows
 Prints one JSON object per config."""
 import json
 import os
@@ -226,3 +229,33 @@ if "mix_incipient" in which:
         print(json.dumps({"config": f"PcSaftMix {'dew' if dew else 'bubble'} point gradients batch={len(keep)}", "ms_mix_jacobian": ms_jac,
                           "ms_point_jacobian_p": ms_p, "ms_point_jacobian_y": ms_y, "ms_point_jacobian_both": ms_both,
                           "both_over_two_mix_jacobian": ms_both / (2.0 * ms_jac), "fused_pays": bool(ms_both < 2.0 * ms_jac)}))
+if "gc_temperature" in which:
+    # bubble / dew temperatures of the gc_batch rows at the pressures bubble_point / dew_point give at the batch temperatures
+    # (so every solved row has an answer: the batch temperature), started 5 % below it, in the class order of the kept rows.
+    # One row per lane, no work queue; the pressure solve it is reported next to runs its fast pass + retry list
+    n = 1_000_000
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    from feos_torch_amd.gc_pcsaft import encode_rows_device
+    rows = encode_rows_device(ident, b["segment_lists"], b["bond_lists"], "cuda")
+    seg = torch.tensor(np.stack([v for _, v in table]), dtype=torch.float64)
+    kab = torch.zeros((len(ident), len(ident)), dtype=torch.float64)
+    for s1, s2, k in b["kab_list"]:
+        kab[ident.index(s1), ident.index(s2)] = k; kab[ident.index(s2), ident.index(s1)] = k
+    tab, S = build_table(seg.cuda(), kab.cuda()), len(ident)
+    phi, T, x, p0 = d(b["phi"]), d(b["T"]), d(b["x"]), d(b["p_init"])
+    order = native.gc_class_order(tab, S, rows)
+    for dew in (False, True):
+        ms_p, rp = timed(lambda: native.gc_bubble_dew(tab, S, rows, phi, T, x, p0, dew, order=order), reps=3)
+        keep = torch.nonzero(~rp["status"]).view(-1)
+        rk, fk, Tk, xk, pk = rows[keep].contiguous(), phi[keep].contiguous(), T[keep].contiguous(), x[keep].contiguous(), rp["p"][keep].contiguous()
+        ok_order = native.gc_class_order(tab, S, rk)
+        T0 = 0.95 * Tk
+        ms, r = timed(lambda: native.gc_bubble_dew_temperature(tab, S, rk, fk, pk, xk, T0, dew, want_iters=True, order=ok_order), reps=3)
+        ms_plain, _ = timed(lambda: native.gc_bubble_dew_temperature(tab, S, rk, fk, pk, xk, T0, dew), reps=3)
+        ok = ~r["status"]
+        err = ((r["t"][ok] / Tk[ok]) - 1.0).abs()
+        print(json.dumps({"config": f"GcPcSaftMix {'dew' if dew else 'bubble'} temperature batch={len(keep)}", "ms": ms, "rows_per_s": len(keep) / ms * 1e3,
+                          "ms_without_class_order": ms_plain, "ms_pressure_solve_1e6": ms_p, "failed": int(r["status"].sum()),
+                          "trials": torch.bincount(r["iters"][ok].long()).tolist(), "round_trip_above_1e-9": int((err > 1e-9).sum()),
+                          "median_rel_round_trip": float(err.median())}))
