@@ -52,15 +52,19 @@ def _encode_molecule(segs, bonds, idx):
     return out
 
 
-def encode_rows(segment_identifier, segment_lists, bond_lists):
-    """[N, 80] uint8 row encoding (layout of include/pcsaft_hip.h), by the native encoder
-    (csrc_host/gc_encode.cpp, built by feos_torch_amd.build.build_host / __graft_entry__.build)."""
+def _encoder():
+    """The native encoder (csrc_host/gc_encode.cpp, built by feos_torch_amd.build.build_host / __graft_entry__.build)."""
     try:
         from . import _gc_encode
     except ImportError as e:  # pragma: no cover
         raise ImportError("feos_torch_amd._gc_encode is not built: run `python -m feos_torch_amd.build`") from e
+    return _gc_encode
+
+
+def encode_rows(segment_identifier, segment_lists, bond_lists):
+    """[N, 80] uint8 row encoding (layout of include/pcsaft_hip.h), by the native encoder."""
     rows = np.zeros((len(segment_lists), 80), dtype=np.uint8)
-    _gc_encode.encode_rows(list(segment_identifier), segment_lists, bond_lists, rows)
+    _encoder().encode_rows(list(segment_identifier), segment_lists, bond_lists, rows)
     return rows
 
 
@@ -68,13 +72,9 @@ def encode_rows_device(segment_identifier, segment_lists, bond_lists, device):
     """[N, 80] uint8 row encoding ON THE DEVICE: the host (csrc_host/gc_encode.cpp::encode_indices) encodes every distinct
     molecule once into a 40-byte table entry and writes two int32 per row; the 80-byte rows are gathered from the table on the
     GPU.  8 instead of 80 bytes per row cross the host memory and the PCIe link (1e6 rows: ~0.03 s of host time)."""
-    try:
-        from . import _gc_encode
-    except ImportError as e:  # pragma: no cover
-        raise ImportError("feos_torch_amd._gc_encode is not built: run `python -m feos_torch_amd.build`") from e
     n = len(segment_lists)
     idx = np.empty((n, 2), dtype=np.int32)
-    table = np.frombuffer(_gc_encode.encode_indices(list(segment_identifier), segment_lists, bond_lists, idx), dtype=np.int64)
+    table = np.frombuffer(_encoder().encode_indices(list(segment_identifier), segment_lists, bond_lists, idx), dtype=np.int64)
     if n == 0:
         return torch.zeros((0, 80), dtype=torch.uint8, device=device)
     tab = torch.from_numpy(table.reshape(-1, 5).copy()).to(device)  # [U, 5] 8-byte fields: seg_id, seg_cnt, bond_a, bond_b, bond_cnt
@@ -115,6 +115,19 @@ def build_table(seg, kab):
     s3 = (0.5 * (sigma[:, None] + sigma[None, :])) ** 3
     ee = eps[:, None] * eps[None, :]
     return torch.cat([seg.reshape(-1), (ee.sqrt() * s3).reshape(-1), (ee * s3).reshape(-1), (1.0 - kab).reshape(-1)]).contiguous()
+
+
+def _device_table(seg, kab, device):
+    """build_table on `device` from a model's host copy of the segment parameters and its k_ab matrix (detached here)."""
+    return build_table(seg.to(device), kab.detach().to(device, torch.float64))
+
+
+def _class_order(model, table):
+    """Class order of the rows of a GcPcSaftMix / GcPcSaft for the kernels' schedule (native.gc_class_order), kept on the
+    model: computed on first use and again after `reduce` — the rows are fixed in between."""
+    if model._order is None or model._order.shape[0] != model.rows.shape[0]:
+        model._order = native.gc_class_order(table, model.S, model.rows)
+    return model._order
 
 
 def _kab_gradient(table, S, rows, ph, T, dA01, dB01):
@@ -158,7 +171,7 @@ class _GcDerivatives(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, kab, phi, temperature, density, *segment_parameters):
         dev = model.device
-        table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
+        table = _device_table(model.seg, kab, dev)
         ph = native._prep(phi, dev, (2,))
         T = native._prep(temperature, dev)
         rho = native._prep(density, dev, (2,))
@@ -181,29 +194,36 @@ class _GcDerivatives(torch.autograd.Function):
 
 
 class _GcBubbleDew(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]], plan.  Dense solve, one compaction plan (its 4-byte row count is the call's only
-    host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the reference drops them
-    inside the native call, src/gc_pcsaft.rs:103-171)."""
+    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew pressure at the temperature `given`, or (solve_t) bubble / dew
+    temperature at the pressure `given`, in one kernel (csrc/gc_temperature.hip); `start` is the initial pressure / the first
+    iterate of the temperature.  Dense solve, one compaction plan (its 4-byte row count is the call's only host
+    synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the reference drops them inside
+    the native call, src/gc_pcsaft.rs:103-171).  A temperature's gradient is the implicit-function theorem on
+    p(theta, T) = p_spec: with J_T = dp/dT (column 6 of pcs_gc_jacobian at the solved state) an upstream gradient g of T is the
+    upstream gradient g' = -g / J_T of the pressure for k_ab, phi and the segment table -- the pressure's own backward
+    kernels -- and dT/dp_spec = 1 / J_T."""
 
     @staticmethod
-    def forward(ctx, dew, model, kab, phi, temperature, molefracs, pressure, check, *segment_parameters):
+    def forward(ctx, dew, model, kab, phi, given, molefracs, start, check, solve_t, *segment_parameters):
         dev, S = model.device, model.S
-        table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
+        table = _device_table(model.seg, kab, dev)
         ph = native._prep(phi, dev, (2,))
-        T = native._prep(temperature, dev)
-        r = native.gc_bubble_dew(table, S, model.rows, ph, T, native._prep(molefracs, dev), native._prep(pressure, dev), dew,
-                                 order=model._class_order(table))
+        known = native._prep(given, dev)
+        args = (table, S, model.rows, ph, known, native._prep(molefracs, dev), native._prep(start, dev), dew)
+        order = _class_order(model, table)
+        r = native.gc_bubble_dew_temperature(*args, order=order) if solve_t else native.gc_bubble_dew(*args, order=order)
         comp = native.Compaction(r["status"])
-        value = comp.gather(r["p"])
-        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, temperature
-        ctx.seg_needs = list(ctx.needs_input_grad[8:])
-        # the class order belongs to the uncompacted rows: used when every row converged
-        order = model._class_order(table) if comp.all_ok else None
+        value = comp.gather(r["t" if solve_t else "p"])
+        at = (lambda: value) if solve_t else (lambda: comp.gather(known))  # temperature of the kept rows: solved or given
+        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, `given`
+        ctx.seg_needs = list(ctx.needs_input_grad[9:])
+        if not comp.all_ok:  # the class order belongs to the uncompacted rows: used when every row converged
+            order = None
         ctx.comp = None
         if any(ctx.needs) or any(ctx.seg_needs):
-            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": comp.gather(T)}
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": at()}
             rho4_ok = comp.gather(r["rho4"])
-            if any(ctx.needs):  # per-row Jacobians for k_ab, phi and T
+            if solve_t or any(ctx.needs):  # per-row Jacobians for k_ab, phi and T (dp/dT: in every gradient of a temperature)
                 keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], keep["T"], rho4_ok, dew, order=order)
             if any(ctx.seg_needs):  # the segment gradient runs in backward, at the densities
                 keep["rho4"] = rho4_ok
@@ -212,13 +232,13 @@ class _GcBubbleDew(torch.autograd.Function):
             ctx.kept = tuple(keep)  # what was saved, by name
             ctx.save_for_backward(*keep.values())
             ctx.comp = comp
-        ctx.dew, ctx.S = bool(dew), S
+        ctx.dew, ctx.S, ctx.solve_t = bool(dew), S, solve_t
         ctx.seg_devs = [p.device for p in segment_parameters]
-        ctx.devs = (kab.device, phi.device, temperature.device)
+        ctx.devs = (kab.device, phi.device, given.device)
         flags = ()
         if check:
             flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.gc_stability(
-                table, S, comp.gather(model.rows), comp.gather(ph), comp.gather(T), feed, order=order)),)
+                table, S, comp.gather(model.rows), comp.gather(ph), at(), feed, order=order)),)
         return (*_shell.finish(ctx, phi.device, [value], r["status"], *flags), comp)
 
     @staticmethod
@@ -226,93 +246,28 @@ class _GcBubbleDew(torch.autograd.Function):
     def backward(ctx, g_value, *_g_flags):
         nseg = len(ctx.seg_needs)
         comp, S = ctx.comp, ctx.S
-        if comp is None:  # nothing the pressure depends on required a gradient
-            return (None,) * (8 + nseg)
+        if comp is None:  # nothing the value depends on required a gradient
+            return (None,) * (9 + nseg)
         kept = dict(zip(ctx.kept, ctx.saved_tensors))
         table, rows, ph, T, jac = kept["table"], kept["rows"], kept["ph"], kept["T"], kept.get("jac")
-        g = g_value.to(table.device).contiguous()
-        gk = gphi = gT = None
-        if ctx.needs[0]:
-            gk = _kab_gradient(table, S, rows, ph, T, g * jac[:, 1], g * jac[:, 4]).to(ctx.devs[0])
-        if ctx.needs[1]:
-            gphi = comp.expand(_phi_gradient(jac, kept["agg"], ph), g).to(ctx.devs[1])
-        if ctx.needs[2]:
-            gT = comp.expand(jac, g, 6, 1).view(comp.n).to(ctx.devs[2])
-        gseg = [None] * nseg
-        if any(ctx.seg_needs):
-            # the whole table in one kernel: sum_i g_i dp_i/d seg[S,8] (the segment-parameter gradient is lazy: it needs
-            # the upstream gradient, so unlike the per-row Jacobians above it runs here, not in forward)
-            G = native.gc_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout=g, order=kept.get("order"))
-            gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
-        return (None, None, gk, gphi, gT, None, None, None, *gseg)
-
-
-class _GcBubbleDewTemperature(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for the solve
-    (csrc/gc_temperature.hip), then as _GcBubbleDew: one compaction plan, gathers only when rows were dropped.  Gradient by the
-    implicit-function theorem on p(theta, T) = p_spec: with J_T = dp/dT (column 6 of pcs_gc_jacobian at the solved state) an
-    upstream gradient g of T is the upstream gradient g' = -g / J_T of the pressure for k_ab, phi and the segment table --
-    the pressure's own backward kernels, no new one -- and dT/dp_spec = 1 / J_T."""
-
-    @staticmethod
-    def forward(ctx, dew, model, kab, phi, pressure, molefracs, temperature, check, *segment_parameters):
-        dev, S = model.device, model.S
-        table = build_table(model.seg.to(dev), kab.detach().to(dev, torch.float64))
-        ph = native._prep(phi, dev, (2,))
-        r = native.gc_bubble_dew_temperature(table, S, model.rows, ph, native._prep(pressure, dev), native._prep(molefracs, dev),
-                                             native._prep(temperature, dev), dew, order=model._class_order(table))
-        comp = native.Compaction(r["status"])
-        value = comp.gather(r["t"])
-        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, pressure
-        ctx.seg_needs = list(ctx.needs_input_grad[8:])
-        # the class order belongs to the uncompacted rows: used when every row converged
-        order = model._class_order(table) if comp.all_ok else None
-        ctx.comp = None
-        if any(ctx.needs) or any(ctx.seg_needs):
-            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": value}
-            rho4_ok = comp.gather(r["rho4"])
-            # dp/dT is needed whatever the gradient goes to
-            keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], value, rho4_ok, dew, order=order)
-            if any(ctx.seg_needs):  # the segment gradient runs in backward, at the densities
-                keep["rho4"] = rho4_ok
-                if order is not None:
-                    keep["order"] = order
-            ctx.kept = tuple(keep)  # what was saved, by name
-            ctx.save_for_backward(*keep.values())
-            ctx.comp = comp
-        ctx.dew, ctx.S = bool(dew), S
-        ctx.seg_devs = [p.device for p in segment_parameters]
-        ctx.devs = (kab.device, phi.device, pressure.device)
-        flags = ()
-        if check:
-            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.gc_stability(
-                table, S, comp.gather(model.rows), comp.gather(ph), value, feed, order=order)),)
-        return (*_shell.finish(ctx, phi.device, [value], r["status"], *flags), comp)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_value, *_g_flags):
-        nseg = len(ctx.seg_needs)
-        comp, S = ctx.comp, ctx.S
-        if comp is None:  # nothing the temperature depends on required a gradient
-            return (None,) * (8 + nseg)
-        kept = dict(zip(ctx.kept, ctx.saved_tensors))
-        table, rows, ph, T, jac = kept["table"], kept["rows"], kept["ph"], kept["T"], kept["jac"]
-        g = g_value.to(table.device).contiguous()
-        inv = 1.0 / jac[:, 6]
-        gp = -g * inv  # upstream gradient of the pressure along p(theta, T) = p_spec
-        gk = gphi = gpres = None
+        g = gp = g_value.to(table.device).contiguous()
+        if ctx.solve_t:
+            inv = 1.0 / jac[:, 6]
+            gp = -g * inv  # upstream gradient of the pressure along p(theta, T) = p_spec
+        gk = gphi = ggiven = None
         if ctx.needs[0]:
             gk = _kab_gradient(table, S, rows, ph, T, gp * jac[:, 1], gp * jac[:, 4]).to(ctx.devs[0])
         if ctx.needs[1]:
             gphi = comp.expand(_phi_gradient(jac, kept["agg"], ph), gp).to(ctx.devs[1])
-        if ctx.needs[2]:
-            gpres = comp.expand(inv, g).view(comp.n).to(ctx.devs[2])
+        if ctx.needs[2]:  # dp/dT, or dT/dp_spec = 1 / J_T
+            ggiven = (comp.expand(inv, g) if ctx.solve_t else comp.expand(jac, g, 6, 1)).view(comp.n).to(ctx.devs[2])
         gseg = [None] * nseg
         if any(ctx.seg_needs):
+            # the whole table in one kernel: sum_i g_i dp_i/d seg[S,8] (the segment-parameter gradient is lazy: it needs
+            # the upstream gradient, so unlike the per-row Jacobians above it runs here, not in forward)
             G = native.gc_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout=gp, order=kept.get("order"))
             gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
-        return (None, None, gk, gphi, gpres, None, None, None, *gseg)
+        return (None, None, gk, gphi, ggiven, None, None, None, None, *gseg)
 
 
 class GcPcSaftMix(_shell.Reducible):
@@ -349,7 +304,7 @@ class GcPcSaftMix(_shell.Reducible):
         self.gc_pcsaft = GcPcSaft._from_model(self)
 
     def _table(self):
-        return build_table(self.seg.to(self.device), self.kab.detach().to(self.device))
+        return _device_table(self.seg, self.kab, self.device)
 
     def helmholtz_energy_density(self, temperature, density, kab=None):
         """a(T, rho_1, rho_2) [A^-3], shape [N, 1] (:116-253); differentiable."""
@@ -364,16 +319,20 @@ class GcPcSaftMix(_shell.Reducible):
 
     def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
         """(p [Pa], nans) (:470-490).  check_stability=True: (p, nans, stable) as PcSaftMix.bubble_point."""
-        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability)
+        return self._point(False, False, temperature, liquid_molefracs, pressure, check_stability)
 
     def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False):
         """(p [Pa], nans) (:492-512).  check_stability=True: (p, nans, stable) as PcSaftMix.dew_point."""
-        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability)
+        return self._point(False, True, temperature, vapor_molefracs, pressure, check_stability)
 
-    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False):
-        # mole fractions and initial pressure do not enter the reference's final formula (:483-490): no gradient flows to them
-        *out, comp = _GcBubbleDew.apply(dew, self, self.kab, self.phi, temperature, _detached(molefracs), _detached(pressure),
-                                        bool(check_stability), *self._segment_parameters)
+    def _point(self, solve_t, dew, given, molefracs, start, check_stability):
+        """bubble / dew pressure at the temperature `given`, or (solve_t) temperature at the pressure `given`"""
+        if solve_t:
+            given = torch.as_tensor(given, dtype=torch.float64)
+        # the mole fractions do not enter the reference's final formula (:483-490) and the initial pressure / first iterate
+        # only starts the search: no gradient flows to either
+        *out, comp = _GcBubbleDew.apply(dew, self, self.kab, self.phi, given, _detached(molefracs), _detached(start),
+                                        bool(check_stability), solve_t, *self._segment_parameters)
         self._reduce(comp)
         return tuple(out)
 
@@ -386,22 +345,13 @@ class GcPcSaftMix(_shell.Reducible):
         where no trial temperature near the first iterate has an equilibrium, where the pressure lies above the bubble line,
         or on a branch on which the pressure falls with the temperature (include/pcsaft_hip.h, pcs_gc_bubble_dew_temperature).
         check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class."""
-        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability)
+        return self._point(True, False, pressure, liquid_molefracs, temperature, check_stability)
 
     def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False):
         """(T [K], nans): the temperature at which the vapour of mole fraction `vapor_molefracs` starts to condense at
         `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
         such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution."""
-        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability)
-
-    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False):
-        # the mole fractions do not enter the reference's final formula and the first iterate only starts the search: no
-        # gradient flows to either
-        *out, comp = _GcBubbleDewTemperature.apply(dew, self, self.kab, self.phi, torch.as_tensor(pressure, dtype=torch.float64),
-                                                   _detached(molefracs), _detached(temperature), bool(check_stability),
-                                                   *self._segment_parameters)
-        self._reduce(comp)
-        return tuple(out)
+        return self._point(True, True, pressure, vapor_molefracs, temperature, check_stability)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction
@@ -409,16 +359,9 @@ class GcPcSaftMix(_shell.Reducible):
         with torch.no_grad():
             table = self._table()
             r = native.gc_stability(table, self.S, self.rows, self.phi, torch.as_tensor(temperature, dtype=torch.float64),
-                                    torch.as_tensor(density, dtype=torch.float64), order=self._class_order(table))
+                                    torch.as_tensor(density, dtype=torch.float64), order=_class_order(self, table))
             out = self.phi.device
             return (r["status"] == 0).to(out), r["tpd"].to(out), r["rho_trial"].to(out)
-
-    def _class_order(self, table):
-        """Class order of the model's rows for the kernels' schedule (native.gc_class_order): computed on first use and
-        again after `reduce` — the rows are fixed in between.  (GcPcSaft borrows this method.)"""
-        if self._order is None or self._order.shape[0] != self.rows.shape[0]:
-            self._order = native.gc_class_order(table, self.S, self.rows)
-        return self._order
 
     def _reduce(self, comp):  # `reduce(nans)` (:514-528) is _shell.Reducible's
         if comp.all_ok:
@@ -463,7 +406,7 @@ class GcPcSaft:
         self.device = _first_gpu(phi)
         self.seg = torch.from_numpy(par).contiguous()
         self.rows = encode_rows_device(ident, segments, bonds, self.device)
-        self.table = build_table(self.seg.to(self.device), _kab_matrix(ident, binary_segment_records, float).to(self.device))
+        self.table = _device_table(self.seg, _kab_matrix(ident, binary_segment_records, float), self.device)
         self.phi = torch.as_tensor(np.asarray(phi, dtype=np.float64))
         self._order = None
 
@@ -479,7 +422,7 @@ class GcPcSaft:
     def _solve(self, temperature, molefracs, pressure, dew):
         t, x, p = (native._as_f64(v, 1) for v in (temperature, molefracs, pressure))
         r = native.gc_bubble_dew(self.table, self.S, self.rows, self.phi, torch.from_numpy(t), torch.from_numpy(x),
-                                 torch.from_numpy(p), dew, order=GcPcSaftMix._class_order(self, self.table))
+                                 torch.from_numpy(p), dew, order=_class_order(self, self.table))
         return native.Compaction(r["status"]).gather(r["rho4"]).cpu().numpy(), r["status"].cpu().numpy()
 
     def bubble_point(self, temperature, liquid_molefracs, pressure):

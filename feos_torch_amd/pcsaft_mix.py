@@ -16,7 +16,7 @@ from . import _shell, native
 from .native import _detached
 
 
-_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, temperature in the [n,19] Jacobian
+_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, temperature (pressure) in the [n,19] Jacobian (quotient)
 
 
 def _incipient_molefrac(rho4, dew):
@@ -40,40 +40,59 @@ def _outputs(ctx, device, values, status, flags, comp):
     return (out[0], *out[len(values):], *out[1:len(values)], comp)
 
 
+def _along_pressure(jac_p, jac_y=None):
+    """Blocks [n,19] of (p[, y]) w.r.t. (parameters, kij, T) -> those of (T[, y]) w.r.t. (parameters, kij, p_spec) along the
+    line p(theta, T) = p_spec (implicit-function theorem, elementwise on the kept rows): dT/dtheta = -J_p[:, :18] / J_p[:, 18],
+    dT/dp_spec = 1 / J_p[:, 18]; dy/dtheta|_p = J_y[:, :18] - J_y[:, 18] J_p[:, :18] / J_p[:, 18], dy/dp_spec = J_y[:, 18] / J_p[:, 18]"""
+    inv = 1.0 / jac_p[:, 18:19]
+    out = [torch.cat((-jac_p[:, :18] * inv, inv), dim=1)]
+    if jac_y is not None:
+        dy_dp = jac_y[:, 18:19] * inv
+        out.append(torch.cat((jac_y[:, :18] - dy_dp * jac_p[:, :18], dy_dp), dim=1))
+    return out
+
+
 class _BubbleDew(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]][, y[n_ok]], plan = bubble / dew pressure.  Dense solve, one compaction plan (its
-    4-byte row count is the call's only host synchronisation), single-kernel gathers only when rows were dropped
-    (native.Compaction; the reference drops them inside the native call, src/pcsaft.rs:216-231).  incipient: y = mole fraction
-    of component 1 in the incipient phase, differentiable like the pressure; the backward pass then takes both Jacobian
-    blocks from ONE pcs_mix_point_jacobian call instead of pcs_mix_jacobian."""
+    """value[n_ok], nans[n][, stable[n_ok]][, y[n_ok]], plan = bubble / dew pressure at the temperature `given`, or
+    (solve_t) bubble / dew temperature at the pressure `given`, in one kernel (csrc/mix_temperature.hip); `start` is the
+    initial pressure / the first iterate of the temperature.  Dense solve, one compaction plan (its 4-byte row count is the
+    call's only host synchronisation), single-kernel gathers only when rows were dropped (native.Compaction; the reference
+    drops them inside the native call, src/pcsaft.rs:216-231).  Gradient to parameters, kij and `given`: pcs_mix_jacobian at
+    the solution, for a temperature turned into the quotients of _along_pressure.  incipient: y = mole fraction of component 1
+    in the incipient phase, differentiable like the value; the backward pass then takes both Jacobian blocks from ONE
+    pcs_mix_point_jacobian call instead of pcs_mix_jacobian."""
 
     @staticmethod
-    def forward(ctx, dew, parameters, kij, temperature, molefracs, pressure, check=False, incipient=False):
+    def forward(ctx, dew, parameters, kij, given, molefracs, start, check=False, incipient=False, solve_t=False):
         dev = native._device_of(parameters)
         par = native._prep(parameters, dev, (2, 8))
         k = native._prep(kij, dev, (2,))
-        T = native._prep(temperature, dev)
-        r = native.mix_bubble_dew(par, k, T, native._prep(molefracs, dev), native._prep(pressure, dev), dew)
+        known = native._prep(given, dev)
+        args = (par, k, known, native._prep(molefracs, dev), native._prep(start, dev), dew)
+        r = native.mix_bubble_dew_temperature(*args) if solve_t else native.mix_bubble_dew(*args)
         comp = native.Compaction(r["status"])
-        values = [comp.gather(r["p"])]
+        value = comp.gather(r["t" if solve_t else "p"])
+        values = [value]
+        # the kept rows' model and temperature (the solved one, or the given one), for the Jacobian and the stability check
+        kept = lambda: (comp.gather(par), comp.gather(k), value if solve_t else comp.gather(known))
         ctx.needs = list(ctx.needs_input_grad[1:4])
         ctx.incipient = incipient
+        blocks = None
         if incipient:
             rho4 = comp.gather(r["rho4"])
             values.append(_incipient_molefrac(rho4, dew))
             ctx.set_materialize_grads(False)  # either upstream gradient may be absent
             if any(ctx.needs):
-                ctx.save_for_backward(*native.mix_point_jacobian(comp.gather(par), comp.gather(k), comp.gather(T), rho4, dew))
-                ctx.comp = comp
+                blocks = native.mix_point_jacobian(*kept(), rho4, dew)
         elif any(ctx.needs):
-            jac = native.mix_jacobian(comp.gather(par), comp.gather(k), comp.gather(T), comp.gather(r["rho4"]), dew)
-            ctx.save_for_backward(jac)
+            blocks = (native.mix_jacobian(*kept(), comp.gather(r["rho4"]), dew),)
+        if blocks is not None:
+            ctx.save_for_backward(*(_along_pressure(*blocks) if solve_t else blocks))
             ctx.comp = comp
-        ctx.in_devices = (parameters.device, kij.device, temperature.device)
+        ctx.in_devices = (parameters.device, kij.device, given.device)
         flags = ()
         if check:
-            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
-                comp.gather(par), comp.gather(k), comp.gather(T), feed)),)
+            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(*kept(), feed)),)
         return _outputs(ctx, parameters.device, values, r["status"], flags, comp)
 
     @staticmethod
@@ -81,69 +100,11 @@ class _BubbleDew(torch.autograd.Function):
     def backward(ctx, g_value, *g_rest):
         if ctx.incipient:
             if g_value is None and g_rest[-2] is None:
-                return (None,) * 8
+                return (None,) * 9
             jac, g = _weighted(ctx.saved_tensors, (g_value, g_rest[-2]))  # outputs: value, nans[, stable], y, plan
         else:
             (jac,), g = ctx.saved_tensors, g_value
-        return (None, *_shell.scatter(ctx.comp, jac, g, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None)
-
-
-_T_COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)))  # parameters, kij, pressure in the [n,19] quotient
-
-
-class _BubbleDewTemperature(torch.autograd.Function):
-    """value[n_ok], nans[n][, stable[n_ok]][, y[n_ok]], plan = bubble / dew temperature at a given pressure.  One kernel for
-    the solve (csrc/mix_temperature.hip), then as _BubbleDew: one compaction plan, gathers only when rows were dropped.
-    Gradient by the implicit-function theorem on p(theta, T) = p_spec with J = pcs_mix_jacobian at the solved state:
-    dT/dtheta = -J[:, :18] / J[:, 18], dT/dp_spec = 1 / J[:, 18] (elementwise on the kept rows).  incipient: y as for
-    _BubbleDew, followed along the same line with (J_p, J_y) from ONE pcs_mix_point_jacobian call:
-    dy/dtheta|_p = J_y[:, :18] - J_y[:, 18] J_p[:, :18] / J_p[:, 18], dy/dp_spec = J_y[:, 18] / J_p[:, 18]."""
-
-    @staticmethod
-    def forward(ctx, dew, parameters, kij, pressure, molefracs, temperature, check=False, incipient=False):
-        dev = native._device_of(parameters)
-        par = native._prep(parameters, dev, (2, 8))
-        k = native._prep(kij, dev, (2,))
-        r = native.mix_bubble_dew_temperature(par, k, native._prep(pressure, dev), native._prep(molefracs, dev),
-                                              native._prep(temperature, dev), dew)
-        comp = native.Compaction(r["status"])
-        value = comp.gather(r["t"])
-        values = [value]
-        ctx.needs = list(ctx.needs_input_grad[1:4])
-        ctx.incipient = incipient
-        if incipient:
-            rho4 = comp.gather(r["rho4"])
-            values.append(_incipient_molefrac(rho4, dew))
-            ctx.set_materialize_grads(False)
-            if any(ctx.needs):
-                jac_p, jac_y = native.mix_point_jacobian(comp.gather(par), comp.gather(k), value, rho4, dew)
-                inv = 1.0 / jac_p[:, 18:19]
-                dy_dp = jac_y[:, 18:19] * inv
-                ctx.save_for_backward(torch.cat((-jac_p[:, :18] * inv, inv), dim=1),
-                                      torch.cat((jac_y[:, :18] - dy_dp * jac_p[:, :18], dy_dp), dim=1))
-                ctx.comp = comp
-        elif any(ctx.needs):
-            jac = native.mix_jacobian(comp.gather(par), comp.gather(k), value, comp.gather(r["rho4"]), dew)
-            inv = 1.0 / jac[:, 18:19]
-            ctx.save_for_backward(torch.cat((-jac[:, :18] * inv, inv), dim=1))
-            ctx.comp = comp
-        ctx.in_devices = (parameters.device, kij.device, pressure.device)
-        flags = ()
-        if check:
-            flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.mix_stability(
-                comp.gather(par), comp.gather(k), value, feed)),)
-        return _outputs(ctx, parameters.device, values, r["status"], flags, comp)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_value, *g_rest):
-        if ctx.incipient:
-            if g_value is None and g_rest[-2] is None:
-                return (None,) * 8
-            quot, g = _weighted(ctx.saved_tensors, (g_value, g_rest[-2]))
-        else:
-            (quot,), g = ctx.saved_tensors, g_value
-        return (None, *_shell.scatter(ctx.comp, quot, g, _T_COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None)
+        return (None, *_shell.scatter(ctx.comp, jac, g, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None, None)
 
 
 class _MixDerivatives(torch.autograd.Function):
@@ -250,12 +211,16 @@ class PcSaftMix(_shell.Reducible):
             return _MixnDerivatives.apply(self._par, temperature, density)
         return _MixDerivatives.apply(self._par, self.kij, temperature, density)
 
-    def _bubble_dew(self, dew, temperature, molefracs, pressure, check_stability=False, incipient_molefracs=False):
+    def _point(self, solve_t, dew, given, molefracs, start, check_stability, incipient_molefracs):
+        """bubble / dew pressure at the temperature `given`, or (solve_t) temperature at the pressure `given`"""
         if self.ncomp != 2:
             raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
-        # mole fractions and initial pressure do not enter the reference's final formula (:435-444): no gradient flows to them
-        *out, comp = _BubbleDew.apply(dew, self._par, self.kij, temperature, _detached(molefracs), _detached(pressure),
-                                      bool(check_stability), bool(incipient_molefracs))
+        if solve_t:
+            given = torch.as_tensor(given, dtype=torch.float64)
+        # the mole fractions do not enter the reference's final formula (:435-444) and the initial pressure / first iterate
+        # only starts the search: no gradient flows to either
+        *out, comp = _BubbleDew.apply(dew, self._par, self.kij, given, _detached(molefracs), _detached(start),
+                                      bool(check_stability), bool(incipient_molefracs), solve_t)
         self._reduce(comp)
         return tuple(out)
 
@@ -268,24 +233,13 @@ class PcSaftMix(_shell.Reducible):
         in the incipient vapour -- (p, nans, y) or (p, nans, stable, y) -- differentiable w.r.t. parameters, kij and
         temperature like p (both gradients from one kernel, pcs_mix_point_jacobian); the other elements are those of the
         default call, bit for bit.  Not part of the reference's class."""
-        return self._bubble_dew(False, temperature, liquid_molefracs, pressure, check_stability, incipient_molefracs)
+        return self._point(False, False, temperature, liquid_molefracs, pressure, check_stability, incipient_molefracs)
 
     def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False, incipient_molefracs=False):
         """(p [Pa], nans) at T [K], vapour mole fraction of component 1, initial pressure [Pa] (:446-468).
         check_stability=True: (p, nans, stable) with the stability of the vapour at the solution (see bubble_point).
         incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid (see bubble_point)."""
-        return self._bubble_dew(True, temperature, vapor_molefracs, pressure, check_stability, incipient_molefracs)
-
-    def _bubble_dew_temperature(self, dew, pressure, molefracs, temperature, check_stability=False, incipient_molefracs=False):
-        if self.ncomp != 2:
-            raise Exception("bubble and dew points are implemented for binary mixtures (src/pcsaft.rs:43-79 takes [N,2,8])")
-        # the mole fractions do not enter the reference's final formula and the first iterate only starts the search: no
-        # gradient flows to either
-        *out, comp = _BubbleDewTemperature.apply(dew, self._par, self.kij, torch.as_tensor(pressure, dtype=torch.float64),
-                                                 _detached(molefracs), _detached(temperature), bool(check_stability),
-                                                 bool(incipient_molefracs))
-        self._reduce(comp)
-        return tuple(out)
+        return self._point(False, True, temperature, vapor_molefracs, pressure, check_stability, incipient_molefracs)
 
     def bubble_temperature(self, pressure, liquid_molefracs, temperature, check_stability=False, incipient_molefracs=False):
         """(T [K], nans): the temperature at which the liquid of mole fraction `liquid_molefracs` (component 1) starts to boil
@@ -298,14 +252,14 @@ class PcSaftMix(_shell.Reducible):
         check_stability=True: (T, nans, stable) as for bubble_point.  incipient_molefracs=True: a last element y [aligned with
         T], the mole fraction of component 1 in the incipient vapour at the solution, differentiable w.r.t. parameters, kij and
         pressure along the line p(theta, T) = pressure.  Not part of the reference's class."""
-        return self._bubble_dew_temperature(False, pressure, liquid_molefracs, temperature, check_stability, incipient_molefracs)
+        return self._point(True, False, pressure, liquid_molefracs, temperature, check_stability, incipient_molefracs)
 
     def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False, incipient_molefracs=False):
         """(T [K], nans): the temperature at which the vapour of mole fraction `vapor_molefracs` starts to condense at
         `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
         such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution.
         incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid."""
-        return self._bubble_dew_temperature(True, pressure, vapor_molefracs, temperature, check_stability, incipient_molefracs)
+        return self._point(True, True, pressure, vapor_molefracs, temperature, check_stability, incipient_molefracs)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's

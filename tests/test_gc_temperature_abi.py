@@ -113,10 +113,10 @@ def test_product_has_no_cpu_fallback_for_the_new_methods():
     if torch.cuda.is_available():
         return  # tests/test_gc_temperature_gpu.py covers the methods where they run
     from feos_torch_amd import _lib
-    from feos_torch_amd.gc_pcsaft import _GcBubbleDewTemperature, GcPcSaftMix
+    from feos_torch_amd.gc_pcsaft import _GcBubbleDew, GcPcSaftMix
 
     assert hasattr(GcPcSaftMix, "bubble_temperature") and hasattr(GcPcSaftMix, "dew_temperature")
-    src = inspect.getsource(_GcBubbleDewTemperature)
+    src = inspect.getsource(_GcBubbleDew)  # one Function serves the pressure and the temperature solve
     assert "native.gc_bubble_dew_temperature(" in src
     # a model cannot even be built without a device (the rows are encoded onto it): the constructor raises the library's error
     ident = ["A", "B"]
