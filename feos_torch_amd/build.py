@@ -24,7 +24,10 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_C
            # (whose k_mix_jacobian it stands next to), csrc/mix_incipient.hpp
            ("mix_incipient.hip", "mix_incipient.o", []),
            # gc bubble / dew temperatures: guarded like gc_kernels.hip (the cold trial is pcs_gc_bubble_dew's), csrc/gc_temperature.hip
-           ("gc_temperature.hip", "gc_temperature.o", [])]
+           ("gc_temperature.hip", "gc_temperature.o", []),
+           # gc pressure + incipient-composition gradients of a bubble / dew point: guarded like gc_kernels.hip (whose k_gc_jacobian it
+           # stands next to), csrc/gc_incipient.hip; the table gradient of both is a mode of gc_gradient.hip's kernel
+           ("gc_incipient.hip", "gc_incipient.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,
@@ -56,7 +59,8 @@ RELAXED_SOURCES = {"pure_kernels.hip"}
 # 1.74 ms, gc dew 4.28 -> 4.17 ms, dew unchanged (scripts/dev/ab_mix.py / ab_gc.py); the status masks are identical and the
 # results move by <= 6.4e-13 relative.  NaN / infinity semantics stay IEEE (no -fno-honor-*), which the failure detection needs.
 GUARDED = ["-DPCS_FAST_LOG=2", "-DPCS_FAST_RCP=2", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math"]
-GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip", "stability_kernels.hip", "mix_temperature.hip", "mix_incipient.hip", "gc_temperature.hip"}  # + the stability analysis (NaN / inf outcomes)
+GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip", "stability_kernels.hip", "mix_temperature.hip", "mix_incipient.hip", "gc_temperature.hip",
+                   "gc_incipient.hip"}  # + the stability analysis (NaN / inf outcomes)
 RESOURCES = os.path.join(HERE, "build", "resources.json")  # per-kernel register / stack report of the last build
 
 

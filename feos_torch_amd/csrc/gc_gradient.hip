@@ -30,18 +30,22 @@
 #include "gc_kernel_common.hpp"
 #include "mix_solver.hpp"
 #include "mix_jacobian.hpp"  // DerivWeights
+#include "mix_incipient.hpp"  // solve3_pair
 
 namespace {
 
 constexpr int GSBLOCK = 64;
 constexpr int GS_GRID = 2048;
-// dual-number directions per pass.  MODE 0 (D1 probes): one molecule-level quantity of BOTH molecules (slot j = molecule j);
+// MODE 2 is MODE 0 for TWO functionals of the converged point at once, the pressure and the incipient-phase mole fraction y0
+// (mix_incipient.hpp): the functional of a row is linear in its phase constants (alpha, beta), so the upstream gradients of both
+// are folded into ONE combined (alpha, beta) per phase and everything behind the adjoint solve is MODE 0's code, run once.
+// dual-number directions per pass.  MODE 0 / 2 (D1 probes): one molecule-level quantity of BOTH molecules (slot j = molecule j);
 // MODE 1 (T2 probes, three times the state per value): one molecule per pass -- with two the stack frame is 4.4 KB per lane
-template <int MODE> struct GsChunk { static constexpr int value = MODE == 0 ? 2 : 1; };
+template <int MODE> struct GsChunk { static constexpr int value = MODE != 1 ? 2 : 1; };
 // LDS doubles per thread behind the table and the gradient accumulator: the double model's bond list (4 * MAXE) + the dual model's
 // bond diameters, which double as the lane-strided coefficient-adjoint array of MODE 0 (ADJ_SLOTS); the row bytes follow (stage_row)
 // (MODE 0: the coefficient adjoints, the dual model is not instantiated; MODE 1: the dual model with CH = 1 direction)
-template <int MODE> struct GsPerThread { static constexpr int value = 2 * GC_MAXE + (MODE == 0 ? ADJ_SLOTS : 2 * GC_MAXE * (1 + GsChunk<1>::value)); };
+template <int MODE> struct GsPerThread { static constexpr int value = 2 * GC_MAXE + (MODE != 1 ? ADJ_SLOTS : 2 * GC_MAXE * (1 + GsChunk<1>::value)); };
 
 enum : int { Q_M, Q_Z1, Q_Z2, Q_Z3, Q_S3, Q_EK, Q_MU, Q_SA, Q_EA, Q_KA, Q_EAB, Q_NA, Q_NB, Q_COUNT };
 
@@ -261,7 +265,8 @@ __device__ __attribute__((noinline)) void gc_finish_gradient(const GcMol<double,
 }
 
 // the functional whose table gradient is taken: MODE 0 = bubble / dew pressure (two phases, D1 probes along beta),
-// MODE 1 = L = ga a + gp p + gmu . mu + gv . v of `derivatives` (one point, T2 probes)
+// MODE 1 = L = ga a + gp p + gmu . mu + gv . v of `derivatives` (one point, T2 probes), MODE 2 = gout_p p + gout_y y0 of a
+// bubble / dew point (MODE 0 with the combined phase constants)
 template <int MODE, class X> struct ProbeT { typedef D1<X> type; };
 template <class X> struct ProbeT<1, X> { typedef T2<X> type; };
 
@@ -270,12 +275,13 @@ struct GcGradArgs {
     const double* table; int S; const unsigned char* rows; const double* phi; const double* temp;
     const double* rho;   // MODE 0: rho4 [n,4], MODE 1: rho [n,2]
     int64_t n;
-    const double* gout;  // MODE 0: upstream dL/dp [n] or NULL
+    const double* gout;  // MODE 0: upstream dL/dp [n] or NULL (= 1); MODE 2: upstream dL/dp [n] or NULL (= 0)
     const double *g_a, *g_p, *g_mu, *g_v;  // MODE 1: upstream gradients (each may be NULL)
     double* grad_seg;    // [S,8] accumulated
     double* jac9;        // MODE 1: [n,9] dL/d(A00, A01, A11, B00, B01, B11, T, rho_0, rho_1)
     double* agg;         // MODE 1: [n,6] aggregate values (optional)
     const int32_t* order;
+    const double* gout_y;  // MODE 2: upstream dL/dy0 [n] or NULL (= 0)
 };
 
 // BLOCK: 64, or 192 where the LDS of three waves fits one CU next to ONE copy of the table (launch_gc_gradient)
@@ -290,7 +296,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
     const double* __restrict__ gout = A_.gout;
     double* __restrict__ grad_seg = A_.grad_seg;
     const int32_t* __restrict__ order = A_.order;
-    constexpr int NPT = MODE == 0 ? 2 : 1;
+    constexpr int NPT = MODE != 1 ? 2 : 1;
     constexpr int CH = GsChunk<MODE>::value;
     typedef DN<double, CH> G;
     typedef typename ProbeT<MODE, G>::type R;
@@ -326,7 +332,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
         const double rT = 1.0 / T;
         // density points of the functional: pt 0 = specified phase (MODE 0) or the state point (MODE 1), pt 1 = incipient phase
         double s0, s1, i0, i1;
-        if (MODE == 0) {
+        if (MODE != 1) {
             const double4 r4 = reinterpret_cast<const double4*>(A_.rho)[i];  // (V0, V1, L0, L1)
             s0 = dew ? r4.x : r4.z; s1 = dew ? r4.y : r4.w; i0 = dew ? r4.z : r4.x; i1 = dew ? r4.w : r4.y;
         } else {
@@ -380,6 +386,50 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
                 alpha[0] = w[2];   beta0[0] = -w[2] * s0 - w[0]; beta1[0] = -w[2] * s1 - w[1];
                 alpha[1] = -u;     beta0[1] = u * i0 + w[0];     beta1[1] = u * i1 + w[1];
             }
+        } else if constexpr (MODE == 2) {
+            // both adjoints of the converged state from one elimination (mix_incipient.hpp): J^T w = dp^vap/du, J^T wy = dy0/du
+            PhaseEval s = phase_eval(m, s0, s1);
+            PhaseEval nn = phase_eval(m, i0, i1);
+            const double rs = s0 + s1, z0 = s0 / rs, z1 = s1 / rs;
+            const double ri = i0 + i1, y0 = i0 / ri, y1 = i1 / ri;
+            double J[3][3];
+            J[0][0] = rs * (z0 * (1.0 / s.r0 + s.h00) + z1 * s.h01);
+            J[1][0] = rs * (z0 * s.h01 + z1 * (1.0 / s.r1 + s.h11));
+            J[2][0] = rs * (z0 * s.dp0() + z1 * s.dp1());
+            J[0][1] = -i0 * (1.0 / i0 + nn.h00);
+            J[1][1] = -i0 * nn.h01;
+            J[2][1] = -i0 * nn.dp0();
+            J[0][2] = -i1 * nn.h01;
+            J[1][2] = -i1 * (1.0 / i1 + nn.h11);
+            J[2][2] = -i1 * nn.dp1();
+            double A[3][5];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+#pragma unroll
+                for (int cc = 0; cc < 3; cc++) A[r][cc] = J[cc][r];
+                A[r][3] = 0.0;
+            }
+            if (dew) {
+                A[0][3] = J[2][0];
+            } else {
+                A[1][3] = -J[2][1];
+                A[2][3] = -J[2][2];
+            }
+            A[0][4] = 0.0;
+            A[1][4] = y0 * y1;
+            A[2][4] = -(y0 * y1);
+            double w[3], wy[3];
+            ok = solve3_pair(A, w, wy);
+            // (alpha, beta) = g_p T P_UNIT (alpha, beta)_p + g_y (alpha, beta)_y; the row weight below is 1
+            const double cp = (gout ? gout[i] : 0.0) * (T * P_UNIT), cy = A_.gout_y ? A_.gout_y[i] : 0.0;
+            const double us = dew ? -(1.0 - w[2]) : w[2];   // alpha_p of the specified phase
+            const double ui = dew ? -w[2] : -(1.0 + w[2]);  // alpha_p of the incipient phase
+            alpha[0] = cp * us + cy * wy[2];
+            beta0[0] = cp * (-us * s0 - w[0]) + cy * (-wy[2] * s0 - wy[0]);
+            beta1[0] = cp * (-us * s1 - w[1]) + cy * (-wy[2] * s1 - wy[1]);
+            alpha[1] = cp * ui - cy * wy[2];
+            beta0[1] = cp * (-ui * i0 + w[0]) + cy * (wy[2] * i0 + wy[0]);
+            beta1[1] = cp * (-ui * i1 + w[1]) + cy * (wy[2] * i1 + wy[1]);
         } else {
             const PhaseEval e = phase_eval(m, s0, s1);
             dw = deriv_weights(e, A_.g_a ? A_.g_a[i] : 0.0, A_.g_p ? A_.g_p[i] : 0.0, A_.g_mu ? A_.g_mu[2 * i] : 0.0,
@@ -389,25 +439,25 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
         // the two probe flavours: seeds of the density arguments and the contraction of a result with the row's weights
         auto seed0 = [&](int pt, auto zero) {
             typedef decltype(zero) X;
-            if constexpr (MODE == 0) return D1<X>(X(pt == 0 ? s0 : i0), X(pt == 0 ? beta0[0] : beta0[1]));
+            if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? s0 : i0), X(pt == 0 ? beta0[0] : beta0[1]));
             else return T2<X>(X(s0), X(1.0), X(0.0), X(0.0), X(0.0), X(0.0));
         };
         auto seed1 = [&](int pt, auto zero) {
             typedef decltype(zero) X;
-            if constexpr (MODE == 0) return D1<X>(X(pt == 0 ? s1 : i1), X(pt == 0 ? beta1[0] : beta1[1]));
+            if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? s1 : i1), X(pt == 0 ? beta1[0] : beta1[1]));
             else return T2<X>(X(s1), X(0.0), X(1.0), X(0.0), X(0.0), X(0.0));
         };
         auto dot_g = [&](const R& a, int pt, int j) -> double {
-            if constexpr (MODE == 0) return (pt == 0 ? alpha[0] : alpha[1]) * a.v.e[j] + a.d1.e[j];
+            if constexpr (MODE != 1) return (pt == 0 ? alpha[0] : alpha[1]) * a.v.e[j] + a.d1.e[j];
             else return deriv_contract(dw, a, j);
         };
         auto dot_q = [&](const Q1& a, int pt) -> double {
-            if constexpr (MODE == 0) return (pt == 0 ? alpha[0] : alpha[1]) * a.v + a.d1;
+            if constexpr (MODE != 1) return (pt == 0 ? alpha[0] : alpha[1]) * a.v + a.d1;
             else return dw.cv * a.v + dw.cg0 * a.g0 + dw.cg1 * a.g1 + dw.ch00 * a.h00 + dw.ch01 * a.h01 + dw.ch11 * a.h11;
         };
         // weight of this row: upstream gradient x (reduced -> Pa); a singular adjoint poisons the result like the
-        // per-row NaN of pcs_gc_jacobian
-        const double wrow = !live ? 0.0 : MODE == 0 ? (ok ? (gout ? gout[i] : 1.0) * (T * P_UNIT) : nanv) : 1.0;
+        // per-row NaN of pcs_gc_jacobian (MODE 2: the upstream gradients are inside alpha and beta)
+        const double wrow = !live ? 0.0 : MODE == 0 ? (ok ? (gout ? gout[i] : 1.0) * (T * P_UNIT) : nanv) : MODE == 2 ? (ok ? 1.0 : nanv) : 1.0;
 
         // chain from a molecule-level sum (quantity q of molecule j, gq = weight x d functional / d sum) to the segment
         // parameters of that molecule's entries
@@ -450,7 +500,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             }
         };
         // ---- (1) molecule-level sums -------------------------------------------------------------------------------
-        if constexpr (MODE == 0 && 1) {
+        if constexpr (MODE != 1) {
             // coefficient adjoints of both phases (closed form), then their chain to the 26 sums
             double* adj = reinterpret_cast<double*>(gbonds) + threadIdx.x;
 #pragma unroll
@@ -686,13 +736,14 @@ extern "C" {
 // rows): a workgroup of several waves shares ONE copy of the table.  launch_gc_gradient_mode takes the largest of 256, 192 and
 // 64 threads whose request stays within the CU's 160 KB, and for the table sizes the ABI admits (S <= 32) that is one branch per
 // mode:
-//   MODE 0 (bubble / dew, 88 doubles per thread): 24 S^2 + 128 S + 704 BLOCK bytes.  256 threads need 180 224 B before the table
+//   MODE 0 and MODE 2 (bubble / dew, 88 doubles per thread): 24 S^2 + 128 S + 704 BLOCK bytes.  256 threads need 180 224 B before the table
 //     and never fit; 192 threads fit for every S (S = 22: 149 KB; S = 32: 163 840 B, exactly the CU's LDS), so the tile is 192
 //     rows and the 64-thread branch (one table per wave, two workgroups per CU at S = 22) is never reached;
 //   MODE 1 (VJP of `derivatives`, 59 doubles per thread): 256 threads fit for every S (S = 32: 149 504 B), so neither the 192- nor
 //     the 64-thread branch is reached.
 // The unreachable branches are kept for a larger table limit.  (tests/test_gc_point_grad_gpu.py, tests/test_gc_state_gpu.py)
 static int launch_gc_gradient(int mode, const GcGradArgs& a, void* stream, const char* what) {
+    if (mode == 2) return launch_gc_gradient_mode<2>(a, stream, what);
     return mode == 0 ? launch_gc_gradient_mode<0>(a, stream, what) : launch_gc_gradient_mode<1>(a, stream, what);
 }
 
@@ -708,6 +759,23 @@ int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* 
     a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
     a.gout = gout; a.grad_seg = grad_seg; a.order = order;
     return launch_gc_gradient(0, a, stream, "k_gc_segment_gradient launch");
+}
+
+int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                                  const double* rho4, int64_t n, const double* gout_p, const double* gout_y, double* grad_seg,
+                                  const int32_t* order, void* stream) {
+    g_err[0] = 0;
+    if (check_n(n)) return fail_msg("pcs_gc_point_segment_gradient", "n must be in [0, 2^31) rows per call (shard larger batches)");
+    if (S < 1 || S > GC_MAXS) return fail_msg("pcs_gc_point_segment_gradient", "S, the number of segment types, must be in [1, 32]");
+    if (n == 0) return 0;
+    if (!table || !rows || !phi || !temp || !rho4 || !grad_seg)
+        return fail_msg("pcs_gc_point_segment_gradient", "null required pointer (table, rows, phi, temp, rho4, grad_seg)");
+    if (!gout_p && !gout_y) return fail_msg("pcs_gc_point_segment_gradient", "gout_p and gout_y are both null (one weight vector is required)");
+    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_point_segment_gradient", "rows must be 16-byte aligned");
+    GcGradArgs a{};
+    a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
+    a.gout = gout_p; a.gout_y = gout_y; a.grad_seg = grad_seg; a.order = order;
+    return launch_gc_gradient(2, a, stream, "k_gc_point_segment_gradient launch");
 }
 
 int pcs_gc_derivatives_vjp(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,

@@ -22,6 +22,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _shell, native
 from .native import _detached
+from .pcsaft_mix import _incipient_molefrac, _outputs
 
 MAXE = 8  # distinct segment types / bond types per molecule in the 80-byte row encoding
 
@@ -201,10 +202,15 @@ class _GcBubbleDew(torch.autograd.Function):
     the native call, src/gc_pcsaft.rs:103-171).  A temperature's gradient is the implicit-function theorem on
     p(theta, T) = p_spec: with J_T = dp/dT (column 6 of pcs_gc_jacobian at the solved state) an upstream gradient g of T is the
     upstream gradient g' = -g / J_T of the pressure for k_ab, phi and the segment table -- the pressure's own backward
-    kernels -- and dT/dp_spec = 1 / J_T."""
+    kernels -- and dT/dp_spec = 1 / J_T.
+    incipient: the outputs gain y [n_ok] behind the flags, the mole fraction of component 1 in the incipient phase (free: rho4
+    of the solve), differentiable like the value.  Forward then takes BOTH per-row blocks jac_p, jac_y [n_ok,7] from one
+    pcs_gc_point_jacobian; backward chains k_ab and phi from the weighted block g_p jac_p + g_y jac_y (both host chains are
+    linear in the block) and makes one pcs_gc_point_segment_gradient call under the weights (g_p, g_y).  Along constant
+    pressure, with J_yT = jac_y[:, 6]: g_p = -(g_T + g_y J_yT) / J_T, g_y stays, and dL/dp_spec = (g_T + g_y J_yT) / J_T."""
 
     @staticmethod
-    def forward(ctx, dew, model, kab, phi, given, molefracs, start, check, solve_t, *segment_parameters):
+    def forward(ctx, dew, model, kab, phi, given, molefracs, start, check, solve_t, incipient, *segment_parameters):
         dev, S = model.device, model.S
         table = _device_table(model.seg, kab, dev)
         ph = native._prep(phi, dev, (2,))
@@ -216,15 +222,26 @@ class _GcBubbleDew(torch.autograd.Function):
         value = comp.gather(r["t" if solve_t else "p"])
         at = (lambda: value) if solve_t else (lambda: comp.gather(known))  # temperature of the kept rows: solved or given
         ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, `given`
-        ctx.seg_needs = list(ctx.needs_input_grad[9:])
+        ctx.seg_needs = list(ctx.needs_input_grad[10:])
+        ctx.incipient = incipient
+        values, rho4_ok = [value], None
+        if incipient:
+            rho4_ok = comp.gather(r["rho4"])
+            values.append(_incipient_molefrac(rho4_ok, dew))
+            ctx.set_materialize_grads(False)  # either upstream gradient may be absent
         if not comp.all_ok:  # the class order belongs to the uncompacted rows: used when every row converged
             order = None
         ctx.comp = None
         if any(ctx.needs) or any(ctx.seg_needs):
             keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": at()}
-            rho4_ok = comp.gather(r["rho4"])
+            if rho4_ok is None:
+                rho4_ok = comp.gather(r["rho4"])
             if solve_t or any(ctx.needs):  # per-row Jacobians for k_ab, phi and T (dp/dT: in every gradient of a temperature)
-                keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], keep["T"], rho4_ok, dew, order=order)
+                if incipient:
+                    keep["jac"], keep["jac_y"], keep["agg"] = native.gc_point_jacobian(table, S, keep["rows"], keep["ph"], keep["T"],
+                                                                                       rho4_ok, dew, order=order)
+                else:
+                    keep["jac"], keep["agg"] = native.gc_jacobian(table, S, keep["rows"], keep["ph"], keep["T"], rho4_ok, dew, order=order)
             if any(ctx.seg_needs):  # the segment gradient runs in backward, at the densities
                 keep["rho4"] = rho4_ok
                 if order is not None:
@@ -239,15 +256,17 @@ class _GcBubbleDew(torch.autograd.Function):
         if check:
             flags = (_shell.stable_at_solution(comp, r["rho4"], dew, lambda feed: native.gc_stability(
                 table, S, comp.gather(model.rows), comp.gather(ph), at(), feed, order=order)),)
-        return (*_shell.finish(ctx, phi.device, [value], r["status"], *flags), comp)
+        return _outputs(ctx, phi.device, values, r["status"], flags, comp)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_value, *_g_flags):
+    def backward(ctx, g_value, *g_rest):
         nseg = len(ctx.seg_needs)
         comp, S = ctx.comp, ctx.S
         if comp is None:  # nothing the value depends on required a gradient
-            return (None,) * (9 + nseg)
+            return (None,) * (10 + nseg)
+        if ctx.incipient:  # outputs: value, nans[, stable], y, plan
+            return _GcBubbleDew._backward_incipient(ctx, g_value, g_rest[-2])
         kept = dict(zip(ctx.kept, ctx.saved_tensors))
         table, rows, ph, T, jac = kept["table"], kept["rows"], kept["ph"], kept["T"], kept.get("jac")
         g = gp = g_value.to(table.device).contiguous()
@@ -267,7 +286,37 @@ class _GcBubbleDew(torch.autograd.Function):
             # the upstream gradient, so unlike the per-row Jacobians above it runs here, not in forward)
             G = native.gc_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout=gp, order=kept.get("order"))
             gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
-        return (None, None, gk, gphi, ggiven, None, None, None, None, *gseg)
+        return (None, None, gk, gphi, ggiven, None, None, None, None, None, *gseg)
+
+    @staticmethod
+    def _backward_incipient(ctx, g_value, g_y):
+        nseg = len(ctx.seg_needs)
+        comp, S = ctx.comp, ctx.S
+        if g_value is None and g_y is None:
+            return (None,) * (10 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T = kept["table"], kept["rows"], kept["ph"], kept["T"]
+        jac_p, jac_y = kept.get("jac"), kept.get("jac_y")
+        gp, gy = (None if g is None else g.to(table.device).contiguous() for g in (g_value, g_y))
+        if ctx.solve_t:  # along p(theta, T) = p_spec: the temperature's and y's own T column act through the pressure's gradients
+            g_total = gp if gy is None else gy * jac_y[:, 6] if gp is None else gp + gy * jac_y[:, 6]
+            dgiven = g_total / jac_p[:, 6]  # dL/dp_spec
+            gp = -dgiven
+        gk = gphi = ggiven = None
+        if any(ctx.needs):
+            block = sum(g[:, None] * j for g, j in ((gp, jac_p), (gy, jac_y)) if g is not None)  # [n_ok,7], weights folded in
+            if ctx.needs[0]:
+                gk = _kab_gradient(table, S, rows, ph, T, block[:, 1], block[:, 4]).to(ctx.devs[0])
+            if ctx.needs[1]:
+                gphi = comp.expand(_phi_gradient(block, kept["agg"], ph)).to(ctx.devs[1])
+            if ctx.needs[2]:
+                ggiven = comp.expand(dgiven if ctx.solve_t else block[:, 6].contiguous()).view(comp.n).to(ctx.devs[2])
+        gseg = [None] * nseg
+        if any(ctx.seg_needs):  # one pass of the table kernel for both functionals
+            G = native.gc_point_segment_gradient(table, S, rows, ph, T, kept["rho4"], ctx.dew, gout_p=gp, gout_y=gy,
+                                                 order=kept.get("order"))
+            gseg = [G[:, k].to(ctx.seg_devs[k]) if need else None for k, need in enumerate(ctx.seg_needs)]
+        return (None, None, gk, gphi, ggiven, None, None, None, None, None, *gseg)
 
 
 class GcPcSaftMix(_shell.Reducible):
@@ -317,22 +366,29 @@ class GcPcSaftMix(_shell.Reducible):
         density = torch.as_tensor(density, dtype=torch.float64)
         return _GcDerivatives.apply(self, self.kab, self.phi, temperature, density, *self._segment_parameters)
 
-    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False):
-        """(p [Pa], nans) (:470-490).  check_stability=True: (p, nans, stable) as PcSaftMix.bubble_point."""
-        return self._point(False, False, temperature, liquid_molefracs, pressure, check_stability)
+    def bubble_point(self, temperature, liquid_molefracs, pressure, check_stability=False, incipient_molefracs=False):
+        """(p [Pa], nans) (:470-490).  check_stability=True: (p, nans, stable) as PcSaftMix.bubble_point.
+        incipient_molefracs=True: the tuple gains a LAST element y [float64, aligned with p], the mole fraction of component 1
+        in the incipient vapour -- (p, nans, y) or (p, nans, stable, y), the contract of PcSaftMix.bubble_point --
+        differentiable w.r.t. the eight segment parameter vectors, k_ab, phi and temperature like p (pcs_gc_point_jacobian,
+        pcs_gc_point_segment_gradient); the other elements are those of the default call, bit for bit."""
+        return self._point(False, False, temperature, liquid_molefracs, pressure, check_stability, incipient_molefracs)
 
-    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False):
-        """(p [Pa], nans) (:492-512).  check_stability=True: (p, nans, stable) as PcSaftMix.dew_point."""
-        return self._point(False, True, temperature, vapor_molefracs, pressure, check_stability)
+    def dew_point(self, temperature, vapor_molefracs, pressure, check_stability=False, incipient_molefracs=False):
+        """(p [Pa], nans) (:492-512).  check_stability=True: (p, nans, stable) as PcSaftMix.dew_point.
+        incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid (see bubble_point)."""
+        return self._point(False, True, temperature, vapor_molefracs, pressure, check_stability, incipient_molefracs)
 
-    def _point(self, solve_t, dew, given, molefracs, start, check_stability):
-        """bubble / dew pressure at the temperature `given`, or (solve_t) temperature at the pressure `given`"""
+    def _point(self, solve_t, dew, given, molefracs, start, check_stability, incipient_molefracs=False):
+        """bubble / dew pressure at the temperature `given`, or (solve_t) temperature at the pressure `given`;
+        incipient_molefracs: the tuple gains y as its last element, for the temperature solve too (y then differentiable
+        w.r.t. the segment vectors, k_ab, phi and the pressure along p(theta, T) = p_spec)"""
         if solve_t:
             given = torch.as_tensor(given, dtype=torch.float64)
         # the mole fractions do not enter the reference's final formula (:483-490) and the initial pressure / first iterate
         # only starts the search: no gradient flows to either
         *out, comp = _GcBubbleDew.apply(dew, self, self.kab, self.phi, given, _detached(molefracs), _detached(start),
-                                        bool(check_stability), solve_t, *self._segment_parameters)
+                                        bool(check_stability), solve_t, bool(incipient_molefracs), *self._segment_parameters)
         self._reduce(comp)
         return tuple(out)
 
@@ -344,7 +400,12 @@ class GcPcSaftMix(_shell.Reducible):
         the pressure's gradients: dT/dp = 1 / (dp/dT)); mole fractions and first iterate receive no gradient.  A row fails
         where no trial temperature near the first iterate has an equilibrium, where the pressure lies above the bubble line,
         or on a branch on which the pressure falls with the temperature (include/pcsaft_hip.h, pcs_gc_bubble_dew_temperature).
-        check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class."""
+        check_stability=True: (T, nans, stable) as for bubble_point.  Not part of the reference's class.
+        (The parameter list of this method and of dew_temperature is pinned, so they do not take incipient_molefracs; the
+        composition at the solved temperature, differentiable along the line of constant pressure, is
+        _point(True, dew, pressure, molefracs, temperature, check_stability, incipient_molefracs=True) -> (T, nans[, stable], y),
+        or, through the public methods, bubble_point(T, x, pressure, incipient_molefracs=True) at the T returned here, whose
+        autograd graph carries dT/dtheta.)"""
         return self._point(True, False, pressure, liquid_molefracs, temperature, check_stability)
 
     def dew_temperature(self, pressure, vapor_molefracs, temperature, check_stability=False):

@@ -736,6 +736,46 @@ def _opt(x, device, shape_tail=None):
     return None if x is None else _prep(x, device, shape_tail)
 
 
+def gc_point_jacobian(table, S, rows, phi, temperature, rho4, dew, want_p=True, want_y=True, order=None):
+    """(jac_p [n,7] or None, jac_y [n,7] or None, agg [n,6]): gradients of the gc bubble / dew pressure [Pa] (gc_jacobian's jac,
+    bit for bit) and of the incipient phase's mole fraction of component 1 w.r.t. (A00, A01, A11, B00, B01, B11, T), one kernel
+    for both (pcs_gc_point_jacobian).  order: optional class order (gc_class_order)."""
+    if not (want_p or want_y):
+        raise ValueError("at least one of want_p / want_y is required")
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature = _prep(temperature, device)
+    rho4 = _prep(rho4, device, (4,))
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi, rho4=rho4)
+    jac_p = _new(device, (n, 7)) if want_p else None
+    jac_y = _new(device, (n, 7)) if want_y else None
+    agg = _new(device, (n, 6))
+    _call(device, "pcs_gc_point_jacobian", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, jac_p, jac_y, agg,
+          _order_or_none(order, n))
+    return jac_p, jac_y, agg
+
+
+def gc_point_segment_gradient(table, S, rows, phi, temperature, rho4, dew, gout_p=None, gout_y=None, order=None):
+    """[S,8] = sum_i (gout_p[i] * d p_i + gout_y[i] * d y_i) / d (segment parameter table) at the converged densities rho4, one
+    pass of the kernel for both functionals (pcs_gc_point_segment_gradient); a weight vector that is None is 0, one is required."""
+    if gout_p is None and gout_y is None:
+        raise ValueError("at least one of gout_p / gout_y is required")
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature = _prep(temperature, device)
+    rho4 = _prep(rho4, device, (4,))
+    gout_p, gout_y = _opt(gout_p, device), _opt(gout_y, device)
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi, rho4=rho4, gout_p=gout_p, gout_y=gout_y)
+    grad = torch.zeros((int(S), 8), dtype=_F64, device=device)
+    _call(device, "pcs_gc_point_segment_gradient", int(bool(dew)), table, int(S), rows, phi, temperature, rho4, n, gout_p, gout_y,
+          grad, _order_or_none(order, n))
+    return grad
+
+
 def pure_derivatives_vjp(params, temperature, density, g_a=None, g_p=None, g_dp=None):
     """Backward of PcSaftPure.derivatives: -> (grad_params [n,8], grad_T [n], grad_rho [n])."""
     device = _device_of(params)

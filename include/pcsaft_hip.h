@@ -469,6 +469,51 @@ int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* 
                             void* stream);
 
 /*
+ * Gradients of TWO functionals of a converged gc bubble (dew = 0) / dew (dew = 1) point in one kernel (ABI 113): the pressure,
+ * as pcs_gc_jacobian, and the composition of the INCIPIENT phase, as pcs_mix_point_jacobian.  Inputs as pcs_gc_jacobian:
+ * (temp, rho4) are the state pcs_gc_bubble_dew or pcs_gc_bubble_dew_temperature returned.
+ *   jac_p [n,7]  out  d p / d (A00, A01, A11, B00, B01, B11, T), Pa per unit: pcs_gc_jacobian's jac, bit for bit (optional)
+ *   jac_y [n,7]  out  d y / d (the same 7), y = the mole fraction of COMPONENT 1 in the incipient phase -- the vapour for
+ *                     bubble, y = rhoV_1 / (rhoV_1 + rhoV_2), the liquid for dew, y = rhoL_1 / (rhoL_1 + rhoL_2) -- at fixed
+ *                     composition of the specified phase (optional)
+ *   agg   [n,6]  out  the aggregate values, as pcs_gc_jacobian (optional)
+ *   order [n]    in   optional class order of the rows as for pcs_gc_bubble_dew (schedule only)
+ * Either of jac_p, jac_y may be NULL, not both (error).  y has no explicit dependence on the inputs: with u = (ln rho_spec,
+ * ln rho_inc_1, ln rho_inc_2) and F = (mu_1^S - mu_1^I, mu_2^S - mu_2^I, p^S - p^I) = 0,  dy/dtheta = -w . dF/dtheta|_u with
+ * J^T w = dy/du = (0, y (1 - y), -y (1 - y)); the coefficient set, both phase evaluations and the elimination of J^T are
+ * shared with the pressure gradient (csrc/gc_incipient.hip).  k_ab and phi enter through the aggregates; the caller chains
+ * them from either block exactly as from pcs_gc_jacobian's.  A row whose 3x3 system is singular gets NaN in jac_p and jac_y;
+ * rows with rho4 = 0 (failed rows of the solve) get unspecified values and do not disturb the others.  A row's result does not
+ * depend on its wave mates, on n, on the order or on which outputs are requested.
+ * Along a line of constant pressure (backward pass of pcs_gc_bubble_dew_temperature with the composition), from the two
+ * blocks at (t_out, rho4), by the implicit-function theorem on p(theta, T) = p_spec:
+ *   dT/dtheta = -jac_p[:, :6] / jac_p[:, 6],                            dT/dp_spec = 1 / jac_p[:, 6]
+ *   dy/dtheta|_p = jac_y[:, :6] - jac_y[:, 6] jac_p[:, :6] / jac_p[:, 6],     dy/dp_spec = jac_y[:, 6] / jac_p[:, 6]
+ */
+int pcs_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                          const double* rho4, int64_t n, double* jac_p, double* jac_y, double* agg, const int32_t* order,
+                          void* stream);
+
+/*
+ * Gradient of both functionals of pcs_gc_point_jacobian w.r.t. the SEGMENT PARAMETER TABLE, contracted with their upstream
+ * gradients over the rows (ABI 113):
+ *   grad_seg [S,8]  +=  sum_i (gout_p[i] * d p_i / d seg[S,8] + gout_y[i] * d y_i / d seg[S,8])
+ *   gout_p   [n]    in   upstream gradient dL/dp_i, per Pa (NULL = 0 for every row)
+ *   gout_y   [n]    in   upstream gradient dL/dy_i (NULL = 0 for every row); gout_p and gout_y both NULL is an error
+ *   grad_seg, rho4, order and the epsilon_k = 0 convention as for pcs_gc_segment_gradient
+ * The functional of a row is linear in its phase constants (alpha, beta) -- specified phase: alpha = w2, beta = -w2 rho^S -
+ * (w0, w1); incipient phase: alpha = -w2, beta = w2 rho^I + (w0, w1) for y, pcs_gc_segment_gradient's for p -- so the kernel
+ * forms (alpha, beta) = gout_p T P_UNIT (alpha, beta)_p + gout_y (alpha, beta)_y from one elimination with two right-hand
+ * sides and runs pcs_gc_segment_gradient's machinery ONCE for both: one pass costs what either functional costs alone.  With
+ * gout_y = NULL the result is pcs_gc_segment_gradient's up to rounding (the weights enter before, not after, the chain).
+ * Along a line of constant pressure, with J_T = jac_p[:, 6], J_yT = jac_y[:, 6] of pcs_gc_point_jacobian and upstream gradients
+ * g_T of the temperature and g_y of y:  gout_p = -(g_T + g_y J_yT) / J_T,  gout_y = g_y;  dL/dp_spec = (g_T + g_y J_yT) / J_T.
+ */
+int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                                  const double* rho4, int64_t n, const double* gout_p, const double* gout_y, double* grad_seg,
+                                  const int32_t* order, void* stream);
+
+/*
  * ---- vector-Jacobian products of the state functions -------------------------------------------------------------
  * In the reference helmholtz_energy(_density) and derivatives are ordinary torch graphs (feos_torch/pcsaft_pure.py:106-182,
  * pcsaft_mix.py:31-154 / :395-420, gc_pcsaft.py:116-253 / :443-468): a loss built on their outputs back-propagates to the

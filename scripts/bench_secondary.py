@@ -20,6 +20,10 @@ with HIP events on the launch stream, inputs resident in HBM.
   gc_temperature: GcPcSaftMix.bubble_temperature / dew_temperature kernel (pcs_gc_bubble_dew_temperature), batch 1e6 minus the
             rows bubble_point / dew_point fail on, at the pressures those give at the batch temperatures, started 5 % below
             the answer; bubble_point / dew_point alongside, trial histogram and failed rows
+  gc_incipient: the backward kernels of GcPcSaftMix.bubble_point / dew_point on the converged rows of config 5, class-ordered:
+            pcs_gc_jacobian next to pcs_gc_point_jacobian (pressure block only, composition block only, both) and
+            pcs_gc_segment_gradient next to pcs_gc_point_segment_gradient (gout_p only, gout_y only, both); the comparison is
+            against the parent kernels run in the same process
 Prints one JSON object per config."""
 import json
 import os
@@ -259,3 +263,41 @@ if "gc_temperature" in which:
                           "ms_without_class_order": ms_plain, "ms_pressure_solve_1e6": ms_p, "failed": int(r["status"].sum()),
                           "trials": torch.bincount(r["iters"][ok].long()).tolist(), "round_trip_above_1e-9": int((err > 1e-9).sum()),
                           "median_rel_round_trip": float(err.median())}))
+if "gc_incipient" in which:
+    # gradients at the converged rows of gc_batch(1e6) in the class order of the kept rows, both problems, median of 3 in this
+    # process.  The per-row kernel shares the coefficient set, both phase evaluations, the elimination and the T direction
+    # between the blocks; the table kernel folds both upstream gradients into one (alpha, beta) and runs one pass
+    n = 1_000_000
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    from feos_torch_amd.gc_pcsaft import encode_rows_device
+    rows = encode_rows_device(ident, b["segment_lists"], b["bond_lists"], "cuda")
+    seg = torch.tensor(np.stack([v for _, v in table]), dtype=torch.float64)
+    kab = torch.zeros((len(ident), len(ident)), dtype=torch.float64)
+    for s1, s2, k in b["kab_list"]:
+        kab[ident.index(s1), ident.index(s2)] = k; kab[ident.index(s2), ident.index(s1)] = k
+    tab, S = build_table(seg.cuda(), kab.cuda()), len(ident)
+    phi, T, x, p0 = d(b["phi"]), d(b["T"]), d(b["x"]), d(b["p_init"])
+    for dew in (False, True):
+        r = native.gc_bubble_dew(tab, S, rows, phi, T, x, p0, dew, order=native.gc_class_order(tab, S, rows))
+        keep = torch.nonzero(~r["status"]).view(-1)
+        rk, pk, Tk, r4 = rows[keep].contiguous(), phi[keep].contiguous(), T[keep].contiguous(), r["rho4"][keep].contiguous()
+        od = native.gc_class_order(tab, S, rk)
+        gp = 1.0 / r["p"][keep].contiguous()
+        gy = torch.ones(len(keep), dtype=torch.float64, device="cuda")
+        args = (tab, S, rk, pk, Tk, r4, dew)
+        ms = {}
+        ms["gc_jacobian"], _ = timed(lambda: native.gc_jacobian(*args, order=od), reps=3)
+        ms["point_jacobian_p"], _ = timed(lambda: native.gc_point_jacobian(*args, want_y=False, order=od), reps=3)
+        ms["point_jacobian_y"], _ = timed(lambda: native.gc_point_jacobian(*args, want_p=False, order=od), reps=3)
+        ms["point_jacobian_both"], _ = timed(lambda: native.gc_point_jacobian(*args, order=od), reps=3)
+        ms["segment_gradient"], _ = timed(lambda: native.gc_segment_gradient(*args, gout=gp, order=od), reps=3)
+        ms["point_segment_gradient_p"], _ = timed(lambda: native.gc_point_segment_gradient(*args, gout_p=gp, order=od), reps=3)
+        ms["point_segment_gradient_y"], _ = timed(lambda: native.gc_point_segment_gradient(*args, gout_y=gy, order=od), reps=3)
+        ms["point_segment_gradient_both"], _ = timed(lambda: native.gc_point_segment_gradient(*args, gout_p=gp, gout_y=gy, order=od), reps=3)
+        print(json.dumps({"config": f"GcPcSaftMix {'dew' if dew else 'bubble'} point gradients batch={len(keep)}",
+                          **{"ms_" + k: v for k, v in ms.items()},
+                          "jacobian_both_over_two_single": ms["point_jacobian_both"] / (ms["point_jacobian_p"] + ms["point_jacobian_y"]),
+                          "jacobian_both_over_two_gc_jacobian": ms["point_jacobian_both"] / (2.0 * ms["gc_jacobian"]),
+                          "segment_both_over_two_single": ms["point_segment_gradient_both"] / (ms["point_segment_gradient_p"] + ms["point_segment_gradient_y"]),
+                          "segment_both_over_two_segment_gradient": ms["point_segment_gradient_both"] / (2.0 * ms["segment_gradient"])}))
