@@ -25,8 +25,8 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_C
            ("mix_incipient.hip", "mix_incipient.o", []),
            # gc bubble / dew temperatures: guarded like gc_kernels.hip (the cold trial is pcs_gc_bubble_dew's), csrc/gc_temperature.hip
            ("gc_temperature.hip", "gc_temperature.o", []),
-           # gc pressure + incipient-composition gradients of a bubble / dew point: guarded like gc_kernels.hip (whose k_gc_jacobian it
-           # stands next to), csrc/gc_incipient.hip; the table gradient of both is a mode of gc_gradient.hip's kernel
+           # gc pressure + incipient-composition gradients of a bubble / dew point (pcs_gc_jacobian and pcs_gc_point_jacobian, one
+           # kernel template): guarded like gc_kernels.hip, csrc/gc_incipient.hip; the table gradient is gc_gradient.hip's kernel
            ("gc_incipient.hip", "gc_incipient.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the

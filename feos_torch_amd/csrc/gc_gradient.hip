@@ -15,7 +15,7 @@
 //   3. the chain from the sums to the parameters of the <= 8 segment types of each molecule is a few multiply-adds per
 //      entry; g_i * dp_i/dtheta is accumulated over the rows of a workgroup in an LDS copy of the [S,8] table
 //      (ds_add_f64) and flushed once per workgroup with global fp64 atomics (persistent grid: 2048 flushes per call).
-// For the bubble / dew pressures only the table gradient is produced here; k_ab, phi and T are pcs_gc_jacobian's.
+// For the bubble / dew pressures only the table gradient is produced here; k_ab, phi and T are pcs_gc_jacobian's (gc_incipient.hip).
 //
 // The same machinery serves the vector-Jacobian product of GcPcSaftMix.derivatives / helmholtz_energy_density
 // (feos_torch/gc_pcsaft.py:443-468; MODE 1): there the functional is L = ga a + gp p + gmu . mu + gv . v at ONE density
@@ -347,11 +347,13 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
         double alpha[2], beta0[2], beta1[2];
         DerivWeights dw;
         bool ok = true;
-        if (MODE == 0) {
-            // adjoint of the converged state (mix_jacobian.hpp): J^T w = dp^vap/du
+        if constexpr (MODE != 1) {
+            // adjoint of the converged state (mix_jacobian.hpp): J^T w = dp^vap/du; MODE 2: and J^T wy = dy0/du from the same
+            // elimination (mix_incipient.hpp)
             PhaseEval s = phase_eval(m, s0, s1);
             PhaseEval nn = phase_eval(m, i0, i1);
             const double rs = s0 + s1, z0 = s0 / rs, z1 = s1 / rs;
+            [[maybe_unused]] const double ri = i0 + i1, y0 = i0 / ri, y1 = i1 / ri;
             double J[3][3];
             J[0][0] = rs * (z0 * (1.0 / s.r0 + s.h00) + z1 * s.h01);
             J[1][0] = rs * (z0 * s.h01 + z1 * (1.0 / s.r1 + s.h11));
@@ -362,7 +364,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             J[0][2] = -i1 * nn.h01;
             J[1][2] = -i1 * (1.0 / i1 + nn.h11);
             J[2][2] = -i1 * nn.dp1();
-            double A[3][4];
+            double A[3][MODE == 2 ? 5 : 4];
 #pragma unroll
             for (int r = 0; r < 3; r++) {
 #pragma unroll
@@ -376,60 +378,34 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
                 A[2][3] = -J[2][2];
             }
             double w[3];
-            ok = solve3(A, w);
-            if (dew) {  // the specified phase is the vapour
-                const double u = 1.0 - w[2];
-                alpha[0] = -u;     beta0[0] = u * s0 - w[0];     beta1[0] = u * s1 - w[1];
-                alpha[1] = -w[2];  beta0[1] = w[2] * i0 + w[0];  beta1[1] = w[2] * i1 + w[1];
+            if constexpr (MODE == 0) {
+                ok = solve3(A, w);
+                if (dew) {  // the specified phase is the vapour
+                    const double u = 1.0 - w[2];
+                    alpha[0] = -u;     beta0[0] = u * s0 - w[0];     beta1[0] = u * s1 - w[1];
+                    alpha[1] = -w[2];  beta0[1] = w[2] * i0 + w[0];  beta1[1] = w[2] * i1 + w[1];
+                } else {
+                    const double u = 1.0 + w[2];
+                    alpha[0] = w[2];   beta0[0] = -w[2] * s0 - w[0]; beta1[0] = -w[2] * s1 - w[1];
+                    alpha[1] = -u;     beta0[1] = u * i0 + w[0];     beta1[1] = u * i1 + w[1];
+                }
             } else {
-                const double u = 1.0 + w[2];
-                alpha[0] = w[2];   beta0[0] = -w[2] * s0 - w[0]; beta1[0] = -w[2] * s1 - w[1];
-                alpha[1] = -u;     beta0[1] = u * i0 + w[0];     beta1[1] = u * i1 + w[1];
+                A[0][4] = 0.0;
+                A[1][4] = y0 * y1;
+                A[2][4] = -(y0 * y1);
+                double wy[3];
+                ok = solve3_pair(A, w, wy);
+                // (alpha, beta) = g_p T P_UNIT (alpha, beta)_p + g_y (alpha, beta)_y; the row weight below is 1
+                const double cp = (gout ? gout[i] : 0.0) * (T * P_UNIT), cy = A_.gout_y ? A_.gout_y[i] : 0.0;
+                const double us = dew ? -(1.0 - w[2]) : w[2];   // alpha_p of the specified phase
+                const double ui = dew ? -w[2] : -(1.0 + w[2]);  // alpha_p of the incipient phase
+                alpha[0] = cp * us + cy * wy[2];
+                beta0[0] = cp * (-us * s0 - w[0]) + cy * (-wy[2] * s0 - wy[0]);
+                beta1[0] = cp * (-us * s1 - w[1]) + cy * (-wy[2] * s1 - wy[1]);
+                alpha[1] = cp * ui - cy * wy[2];
+                beta0[1] = cp * (-ui * i0 + w[0]) + cy * (wy[2] * i0 + wy[0]);
+                beta1[1] = cp * (-ui * i1 + w[1]) + cy * (wy[2] * i1 + wy[1]);
             }
-        } else if constexpr (MODE == 2) {
-            // both adjoints of the converged state from one elimination (mix_incipient.hpp): J^T w = dp^vap/du, J^T wy = dy0/du
-            PhaseEval s = phase_eval(m, s0, s1);
-            PhaseEval nn = phase_eval(m, i0, i1);
-            const double rs = s0 + s1, z0 = s0 / rs, z1 = s1 / rs;
-            const double ri = i0 + i1, y0 = i0 / ri, y1 = i1 / ri;
-            double J[3][3];
-            J[0][0] = rs * (z0 * (1.0 / s.r0 + s.h00) + z1 * s.h01);
-            J[1][0] = rs * (z0 * s.h01 + z1 * (1.0 / s.r1 + s.h11));
-            J[2][0] = rs * (z0 * s.dp0() + z1 * s.dp1());
-            J[0][1] = -i0 * (1.0 / i0 + nn.h00);
-            J[1][1] = -i0 * nn.h01;
-            J[2][1] = -i0 * nn.dp0();
-            J[0][2] = -i1 * nn.h01;
-            J[1][2] = -i1 * (1.0 / i1 + nn.h11);
-            J[2][2] = -i1 * nn.dp1();
-            double A[3][5];
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-#pragma unroll
-                for (int cc = 0; cc < 3; cc++) A[r][cc] = J[cc][r];
-                A[r][3] = 0.0;
-            }
-            if (dew) {
-                A[0][3] = J[2][0];
-            } else {
-                A[1][3] = -J[2][1];
-                A[2][3] = -J[2][2];
-            }
-            A[0][4] = 0.0;
-            A[1][4] = y0 * y1;
-            A[2][4] = -(y0 * y1);
-            double w[3], wy[3];
-            ok = solve3_pair(A, w, wy);
-            // (alpha, beta) = g_p T P_UNIT (alpha, beta)_p + g_y (alpha, beta)_y; the row weight below is 1
-            const double cp = (gout ? gout[i] : 0.0) * (T * P_UNIT), cy = A_.gout_y ? A_.gout_y[i] : 0.0;
-            const double us = dew ? -(1.0 - w[2]) : w[2];   // alpha_p of the specified phase
-            const double ui = dew ? -w[2] : -(1.0 + w[2]);  // alpha_p of the incipient phase
-            alpha[0] = cp * us + cy * wy[2];
-            beta0[0] = cp * (-us * s0 - w[0]) + cy * (-wy[2] * s0 - wy[0]);
-            beta1[0] = cp * (-us * s1 - w[1]) + cy * (-wy[2] * s1 - wy[1]);
-            alpha[1] = cp * ui - cy * wy[2];
-            beta0[1] = cp * (-ui * i0 + w[0]) + cy * (wy[2] * i0 + wy[0]);
-            beta1[1] = cp * (-ui * i1 + w[1]) + cy * (wy[2] * i1 + wy[1]);
         } else {
             const PhaseEval e = phase_eval(m, s0, s1);
             dw = deriv_weights(e, A_.g_a ? A_.g_a[i] : 0.0, A_.g_p ? A_.g_p[i] : 0.0, A_.g_mu ? A_.g_mu[2 * i] : 0.0,
@@ -456,7 +432,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             else return dw.cv * a.v + dw.cg0 * a.g0 + dw.cg1 * a.g1 + dw.ch00 * a.h00 + dw.ch01 * a.h01 + dw.ch11 * a.h11;
         };
         // weight of this row: upstream gradient x (reduced -> Pa); a singular adjoint poisons the result like the
-        // per-row NaN of pcs_gc_jacobian (MODE 2: the upstream gradients are inside alpha and beta)
+        // per-row NaN of k_gc_point_jacobian (MODE 2: the upstream gradients are inside alpha and beta)
         const double wrow = !live ? 0.0 : MODE == 0 ? (ok ? (gout ? gout[i] : 1.0) * (T * P_UNIT) : nanv) : MODE == 2 ? (ok ? 1.0 : nanv) : 1.0;
 
         // chain from a molecule-level sum (quantity q of molecule j, gq = weight x d functional / d sum) to the segment

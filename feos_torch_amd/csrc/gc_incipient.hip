@@ -1,21 +1,23 @@
 // Gradients of the gc bubble / dew pressure AND of the incipient-phase mole fraction at a converged bubble / dew point w.r.t.
-// the six dispersion aggregates and T (see include/pcsaft_hip.h: pcs_gc_point_jacobian; the mathematics is mix_incipient.hpp's).
-// Own translation unit, compiled with the flags of gc_kernels.hip (feos_torch_amd/build.py, GUARDED_SOURCES), whose k_gc_jacobian
-// it stands next to: the per-row backward pass of GcPcSaftMix.bubble_point / dew_point / bubble_temperature / dew_temperature
-// with incipient_molefracs=True.  k_gc_jacobian itself is untouched and stays the backward pass of the default calls.
+// the six dispersion aggregates and T (see include/pcsaft_hip.h: pcs_gc_jacobian, pcs_gc_point_jacobian; the mathematics is
+// mix_jacobian.hpp's and mix_incipient.hpp's).  Own translation unit, compiled with the flags of gc_kernels.hip
+// (feos_torch_amd/build.py, GUARDED_SOURCES).  One kernel template is the per-row backward pass of every GcPcSaftMix bubble / dew
+// call: pcs_gc_jacobian (the default calls) launches <true, false>, pcs_gc_point_jacobian (incipient_molefracs=True) the
+// instantiation for the blocks it is asked for.
 //
-// Same state and equations as k_gc_jacobian: u = (ln rho_spec, ln rho_inc_0, ln rho_inc_1), F = (mu_0^S - mu_0^I, mu_1^S - mu_1^I,
-// p^S - p^I) = 0, J = dF/du.  The pressure block is k_gc_jacobian's, operation for operation (its bits are pinned by
-// tests/test_gc_incipient_gpu.py); y0 = rho_inc_0 / (rho_inc_0 + rho_inc_1) has no explicit dependence on theta:
+// State and equations: u = (ln rho_spec, ln rho_inc_0, ln rho_inc_1), F = (mu_0^S - mu_0^I, mu_1^S - mu_1^I, p^S - p^I) = 0,
+// J = dF/du, J^T w = dp^vap/du (implicit-function form).  k_ab and phi enter the model only through the aggregates
+// (feos_torch/gc_pcsaft.py:181-194), the host chains them (gc_pcsaft.py in this package).  y0 = rho_inc_0 / (rho_inc_0 +
+// rho_inc_1) has no explicit dependence on theta:
 //     J^T w_y = dy0/du = (0, y0 y1, -y0 y1),    dy0/dtheta = -w_y . dF/dtheta|_u
 // without a unit factor and without the p_red term of the temperature column.  One coefficient set, two phase evaluations, one
 // elimination with two right-hand sides (solve3_pair), one dual direction (T) contracted once per requested functional.
-// One kernel template, instantiated per set of requested blocks, so that the pressure block's statements stand unguarded
-// exactly as in k_gc_jacobian; the composition block follows in statements of its own that read the phase derivatives through
-// `detached` copies.  Both matter for the bits of jac_p: this unit is compiled with -fassociative-math, and a subexpression
-// shared between the blocks, or a branch around the pressure block, moved its rounding (measured: up to 1.3e-13 relative on
-// 40 % of the entries).
-// Launch shape and LDS of k_gc_jacobian: 256-thread workgroups that share one copy of the table, 59 doubles of LDS per thread.
+// The bits of the pressure block (jac_p, agg) are pinned, row by row, by tests/golden/gc_jacobian_bits.json
+// (tests/test_gc_jacobian_bits_gpu.py), in every instantiation that writes it.  For that the template is instantiated per set
+// of requested blocks, so that the pressure block's statements stand unguarded; the composition block follows in statements of
+// its own that read the phase derivatives through `detached` copies.  Both matter for the bits of jac_p: this unit is compiled
+// with -fassociative-math, and a subexpression shared between the blocks, or a branch around the pressure block, moved its
+// rounding (measured: up to 1.3e-13 relative on 40 % of the entries).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,13 +33,16 @@ using namespace pcs_abi;
 
 namespace {
 
+// 59 doubles of LDS per thread (bond diameters of the double and the dual model, row bytes); a 256-thread workgroup shares ONE
+// copy of the table among four waves (S = 22: 131 KB, S = 32: 144 KB of the CU's 160 KB) -- 64-thread workgroups fit three times
+// (one wave each): the kernel holds a full register file per wave, so resident waves per CU are what counts
 constexpr int GPJBLOCK = 256;
 constexpr int GC_DIRS = 7;   // A00, A01, A11, B00, B01, B11, T
 constexpr int GC_CHUNK = 1;  // the only dual-number direction is T
 
 // A copy of x the compiler cannot identify with x (no instruction).  The composition block reads the phase derivatives through
 // it: shared with the pressure block as common subexpressions they would end the pressure block's expression trees at other
-// places than in k_gc_jacobian, and under -fassociative-math the pressure columns would round differently.
+// places than in <true, false>, and under -fassociative-math the pressure columns would leave their pinned bits.
 __device__ __forceinline__ double detached(double x) {
     asm volatile("" : "+v"(x));
     return x;
@@ -115,7 +120,8 @@ __global__ __launch_bounds__(GPJBLOCK) void k_gc_point_jacobian(int dew, const d
     double* g = jac_p + GC_DIRS * i;
     double* gy = jac_y + GC_DIRS * i;
 
-    // (1) the six aggregates: closed form from the dispersion factors.  The pressure block is k_gc_jacobian's text; the
+    // (1) the six aggregates: the dispersion term is linear in them, a_disp = F1 sum_k A_k q_k + F2 sum_k B_k q_k with
+    //     q = (r0^2, r0 r1, r1^2): d(a, da/dr0, da/dr1)/dA_k = (F1 q_k, dF1/dr0 q_k + F1 dq_k/dr0, ...) -- no dual pass.  The
     //     composition block follows in statements of its own on detached copies (see `detached`): y0 has no explicit term
     {
         typedef T1<double> Q;
@@ -206,21 +212,10 @@ __global__ __launch_bounds__(GPJBLOCK) void k_gc_point_jacobian(int dew, const d
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int pcs_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
-                          const double* rho4, int64_t n, double* jac_p, double* jac_y, double* agg, const int32_t* order,
-                          void* stream) {
-    g_err[0] = 0;
-    if (check_n(n)) return fail_msg("pcs_gc_point_jacobian", "n must be in [0, 2^31) rows per call (shard larger batches)");
-    if (S < 1 || S > GC_MAXS) return fail_msg("pcs_gc_point_jacobian", "S, the number of segment types, must be in [1, 32]");
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho4)
-        return fail_msg("pcs_gc_point_jacobian", "null required pointer (table, rows, phi, temp, rho4)");
-    if (!jac_p && !jac_y) return fail_msg("pcs_gc_point_jacobian", "jac_p and jac_y are both null (one output is required)");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_point_jacobian", "rows must be 16-byte aligned");
+// The one launch behind both entry points.  jac_y = nullptr, as pcs_gc_jacobian passes it, selects <true, false>
+int launch_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                             const double* rho4, int64_t n, double* jac_p, double* jac_y, double* agg, const int32_t* order,
+                             void* stream) {
     const unsigned grid = grid_for(n, GPJBLOCK);
     // double model: 2*MAXE doubles per thread; dual model dab: 2*MAXE * (1 + GC_CHUNK) doubles per thread; the row bytes
     const size_t lds = gc_lds_bytes(S, GPJBLOCK, 2 * GC_MAXE + 2 * GC_MAXE * (1 + GC_CHUNK) + GC_ROW_LDS_DOUBLES);
@@ -237,6 +232,34 @@ int pcs_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* ro
                                                                                   : launch(k_gc_point_jacobian<false, true>))
         return e;
     return launched("k_gc_point_jacobian launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                    const double* rho4, int64_t n, double* jac, double* agg, const int32_t* order, void* stream) {
+    g_err[0] = 0;
+    if (int e = gc_check(S, n)) return e;
+    if (n == 0) return 0;
+    if (!table || !rows || !phi || !temp || !rho4 || !jac) return fail_msg("pcs_gc_jacobian: null required pointer");
+    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_jacobian: rows must be 16-byte aligned");
+    return launch_gc_point_jacobian(dew, table, S, rows, phi, temp, rho4, n, jac, nullptr, agg, order, stream);
+}
+
+int pcs_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                          const double* rho4, int64_t n, double* jac_p, double* jac_y, double* agg, const int32_t* order,
+                          void* stream) {
+    g_err[0] = 0;
+    if (check_n(n)) return fail_msg("pcs_gc_point_jacobian", "n must be in [0, 2^31) rows per call (shard larger batches)");
+    if (S < 1 || S > GC_MAXS) return fail_msg("pcs_gc_point_jacobian", "S, the number of segment types, must be in [1, 32]");
+    if (n == 0) return 0;
+    if (!table || !rows || !phi || !temp || !rho4)
+        return fail_msg("pcs_gc_point_jacobian", "null required pointer (table, rows, phi, temp, rho4)");
+    if (!jac_p && !jac_y) return fail_msg("pcs_gc_point_jacobian", "jac_p and jac_y are both null (one output is required)");
+    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_point_jacobian", "rows must be 16-byte aligned");
+    return launch_gc_point_jacobian(dew, table, S, rows, phi, temp, rho4, n, jac_p, jac_y, agg, order, stream);
 }
 
 }  // extern "C"

@@ -19,10 +19,6 @@ using namespace pcs_abi;
 namespace {
 
 constexpr int GBLOCK = 128;
-// Jacobian kernel: 59 doubles of LDS per thread (bond diameters of the double and the dual model, row bytes); a 256-thread workgroup
-// shares ONE copy of the table among four waves (S = 22: 131 KB, S = 32: 144 KB of the CU's 160 KB) -- 64-thread workgroups fit three
-// times (one wave each): the kernel holds a full register file per wave, so resident waves per CU are what counts
-constexpr int GJBLOCK = 256;
 
 // fast-pass caps (mix_solver.hpp).  A/B on the synthetic dew batch (scripts/dev/ab_gc.py): 12/12: 9.0 ms, 6/8: 7.9, 4/8: 8.4, 7/7: 8.6
 constexpr int GC_FAST_SS = 6, GC_FAST_NEWTON = 8;
@@ -141,131 +137,6 @@ __global__ __launch_bounds__(GBLOCK) void k_gc_derivatives(const double* __restr
     }
 }
 
-// gradient of the bubble / dew pressure w.r.t. the six dispersion aggregates and T (implicit-
-// function form, see mix_jacobian.hpp); k_ab and phi enter the model only through the
-// aggregates (feos_torch/gc_pcsaft.py:181-194), the host chains them (gc_pcsaft.py in this package).
-constexpr int GC_DIRS = 7;   // A00, A01, A11, B00, B01, B11, T
-constexpr int GC_CHUNK = 1;  // the only dual-number direction left is T
-
-__global__ __launch_bounds__(GJBLOCK) void k_gc_jacobian(int dew, const double* __restrict__ table, int S,
-                                                         const unsigned char* __restrict__ rows,
-                                                         const double* __restrict__ phi,
-                                                         const double* __restrict__ temp,
-                                                         const double* __restrict__ rho4, int64_t n,
-                                                         double* __restrict__ jac, double* __restrict__ agg,
-                                                         const int32_t* __restrict__ order) {
-    typedef DN<double, GC_CHUNK> G;
-    typedef T1<G> R;
-    extern __shared__ double lds[];
-    GcTable tb = stage_table(table, S, lds);
-    double* bonds = lds + gc_table_doubles(S);                       // double model: [2*MAXE dab] x block
-    G* gbonds = reinterpret_cast<G*>(bonds + 2 * GC_MAXE * GJBLOCK);  // dual model dab
-    int64_t i = (int64_t)blockIdx.x * GJBLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (order) {  // class order of the rows (see pcs_gc_bubble_dew)
-        i = order[i];
-        if (i < 0 || i >= n) return;
-    }
-    // (row bytes staged behind the dual model's bond area)
-    const unsigned char* row = stage_row(rows + (size_t)i * GC_ROW_BYTES, bonds + (2 * GC_MAXE + 2 * GC_MAXE * (1 + GC_CHUNK)) * GJBLOCK);
-    const double T = temp[i], ph0 = phi[2 * i], ph1 = phi[2 * i + 1];
-    const double4 r4 = reinterpret_cast<const double4*>(rho4)[i];  // (V0, V1, L0, L1)
-    const double s0 = dew ? r4.x : r4.z, s1 = dew ? r4.y : r4.w, i0 = dew ? r4.z : r4.x, i1 = dew ? r4.w : r4.y;
-    GcModelT<double> m;
-    m.c.bond_dab = bonds + threadIdx.x;
-    m.c.stride = GJBLOCK;
-    gc_coef<double>(m.c, row, tb, ph0, ph1, T);
-    if (agg) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { agg[6 * i + k] = m.c.A[k]; agg[6 * i + 3 + k] = m.c.B[k]; }
-    }
-    PhaseEval s = phase_eval(m, s0, s1);
-    PhaseEval nn = phase_eval(m, i0, i1);
-    const double rs = s0 + s1, z0 = s0 / rs, z1 = s1 / rs;
-    double J[3][3];
-    J[0][0] = rs * (z0 * (1.0 / s.r0 + s.h00) + z1 * s.h01);
-    J[1][0] = rs * (z0 * s.h01 + z1 * (1.0 / s.r1 + s.h11));
-    J[2][0] = rs * (z0 * s.dp0() + z1 * s.dp1());
-    J[0][1] = -i0 * (1.0 / i0 + nn.h00);
-    J[1][1] = -i0 * nn.h01;
-    J[2][1] = -i0 * nn.dp0();
-    J[0][2] = -i1 * nn.h01;
-    J[1][2] = -i1 * (1.0 / i1 + nn.h11);
-    J[2][2] = -i1 * nn.dp1();
-    double A[3][4];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int cc = 0; cc < 3; cc++) A[r][cc] = J[cc][r];
-        A[r][3] = 0.0;
-    }
-    if (dew) {
-        A[0][3] = J[2][0];
-    } else {
-        A[1][3] = -J[2][1];
-        A[2][3] = -J[2][2];
-    }
-    double w[3];
-    const bool ok = solve3(A, w);
-    const double p_red = dew ? s.p() : nn.p();
-    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
-    double* g = jac + GC_DIRS * i;
-
-    // (1) the six aggregates: the dispersion term is linear in them, a_disp = F1 sum_k A_k q_k + F2 sum_k B_k q_k with
-    //     q = (r0^2, r0 r1, r1^2): d(a, da/dr0, da/dr1)/dA_k = (F1 q_k, dF1/dr0 q_k + F1 dq_k/dr0, ...) -- no dual pass
-    {
-        typedef T1<double> Q;
-        Q F1s, F2s, F1i, F2i;
-        dispersion_factors(m.c, Q(s0, 1.0, 0.0), Q(s1, 0.0, 1.0), F1s, F2s);
-        dispersion_factors(m.c, Q(i0, 1.0, 0.0), Q(i1, 0.0, 1.0), F1i, F2i);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            // q_k and its gradient in both phases
-            const double qs = (k == 0) ? s0 * s0 : (k == 1 ? s0 * s1 : s1 * s1);
-            const double qs0 = (k == 0) ? 2.0 * s0 : (k == 1 ? s1 : 0.0), qs1 = (k == 0) ? 0.0 : (k == 1 ? s0 : 2.0 * s1);
-            const double qi = (k == 0) ? i0 * i0 : (k == 1 ? i0 * i1 : i1 * i1);
-            const double qi0 = (k == 0) ? 2.0 * i0 : (k == 1 ? i1 : 0.0), qi1 = (k == 0) ? 0.0 : (k == 1 ? i0 : 2.0 * i1);
-#pragma unroll
-            for (int ab = 0; ab < 2; ab++) {
-                const Q& Fs = ab == 0 ? F1s : F2s;
-                const Q& Fi = ab == 0 ? F1i : F2i;
-                const double aS = Fs.v * qs, gS0 = Fs.g0 * qs + Fs.v * qs0, gS1 = Fs.g1 * qs + Fs.v * qs1;
-                const double aI = Fi.v * qi, gI0 = Fi.g0 * qi + Fi.v * qi0, gI1 = Fi.g1 * qi + Fi.v * qi1;
-                const double dF0 = gS0 - gI0, dF1 = gS1 - gI1;
-                const double dpS = -aS + s0 * gS0 + s1 * gS1;
-                const double dpI = -aI + i0 * gI0 + i1 * gI1;
-                const double dp = (dew ? dpS : dpI) - (w[0] * dF0 + w[1] * dF1 + w[2] * (dpS - dpI));
-                g[3 * ab + k] = ok ? dp * T * P_UNIT : nanv;
-            }
-        }
-    }
-
-    // (2) T: one dual-number direction, both phases through one evaluation site
-    {
-        G gT;
-        gT.v = T;
-        gT.e[0] = 1.0;
-        GcCoef<G> c;
-        c.bond_dab = gbonds + threadIdx.x;
-        c.bond_cnt = m.c.bond_cnt;  // counts are shared (written identically)
-        c.stride = GJBLOCK;
-        gc_coef<G>(c, row, tb, ph0, ph1, gT);
-        double av[2], ag0[2], ag1[2];
-#pragma unroll 1
-        for (int ph = 0; ph < 2; ph++) {
-            const double q0 = ph == 0 ? s0 : i0, q1 = ph == 0 ? s1 : i1;
-            R a = gc_a_tangent<G, R>(c, R(G(q0), G(1.0), G(0.0)), R(G(q1), G(0.0), G(1.0)));
-            if (ph == 0) { av[0] = a.v.e[0]; ag0[0] = a.g0.e[0]; ag1[0] = a.g1.e[0]; }
-            else { av[1] = a.v.e[0]; ag0[1] = a.g0.e[0]; ag1[1] = a.g1.e[0]; }
-        }
-        const double dF0 = ag0[0] - ag0[1], dF1 = ag1[0] - ag1[1];
-        const double dpS = -av[0] + s0 * ag0[0] + s1 * ag1[0];
-        const double dpI = -av[1] + i0 * ag0[1] + i1 * ag1[1];
-        const double dp = (dew ? dpS : dpI) - (w[0] * dF0 + w[1] * dF1 + w[2] * (dpS - dpI));
-        g[6] = ok ? dp * T * P_UNIT + p_red * P_UNIT : nanv;
-    }
-}
-
 // fast pass over all rows and, with a work list, the robust pass over the rows it gave up on
 template <bool DEW>
 void launch_gc_bubble_dew(unsigned grid, size_t lds, hipStream_t s, const double* table, int S, const uint8_t* rows, const double* phi,
@@ -315,25 +186,6 @@ int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const do
     hipLaunchKernelGGL(k_gc_derivatives, dim3(grid), dim3(GBLOCK), gc_lds_bytes(S, GBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES), as_stream(stream),
                        table, S, rows, phi, temp, rho, n, a, p, mu, v);
     return launched("k_gc_derivatives launch");
-}
-
-int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
-                    const double* rho4, int64_t n, double* jac, double* agg, const int32_t* order, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho4 || !jac) return fail_msg("pcs_gc_jacobian: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_jacobian: rows must be 16-byte aligned");
-    const unsigned grid = grid_for(n, GJBLOCK);
-    // double model: 2*MAXE doubles per thread; dual model dab: 2*MAXE * (1 + GC_CHUNK) doubles per thread
-    const size_t lds = gc_lds_bytes(S, GJBLOCK, 2 * GC_MAXE + 2 * GC_MAXE * (1 + GC_CHUNK) + GC_ROW_LDS_DOUBLES);
-    if (lds > 64 * 1024) {  // above the default dynamic-LDS limit
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gc_jacobian), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return fail("k_gc_jacobian attribute", ea);
-    }
-    hipLaunchKernelGGL(k_gc_jacobian, dim3(grid), dim3(GJBLOCK), lds, as_stream(stream), dew, table, S, rows, phi, temp,
-                       rho4, n, jac, agg, order);
-    return launched("k_gc_jacobian launch");
 }
 
 }  // extern "C"

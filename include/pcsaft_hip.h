@@ -449,6 +449,7 @@ int pcs_gc_stability(const double* table, int S, const uint8_t* rows, const doub
  *               (feos_torch/gc_pcsaft.py:177-194) — k_ab and phi enter the model only through them;
  *   agg [n,6] = the aggregate values (optional);
  *   order [n]   = optional class order of the rows as for pcs_gc_bubble_dew (schedule only).
+ * The pressure-only launch of pcs_gc_point_jacobian's kernel (csrc/gc_incipient.hip).
  */
 int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                     const double* rho4, int64_t n, double* jac, double* agg, const int32_t* order, void* stream);
@@ -471,8 +472,10 @@ int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* 
 /*
  * Gradients of TWO functionals of a converged gc bubble (dew = 0) / dew (dew = 1) point in one kernel (ABI 113): the pressure,
  * as pcs_gc_jacobian, and the composition of the INCIPIENT phase, as pcs_mix_point_jacobian.  Inputs as pcs_gc_jacobian:
- * (temp, rho4) are the state pcs_gc_bubble_dew or pcs_gc_bubble_dew_temperature returned.
- *   jac_p [n,7]  out  d p / d (A00, A01, A11, B00, B01, B11, T), Pa per unit: pcs_gc_jacobian's jac, bit for bit (optional)
+ * (temp, rho4) are the state pcs_gc_bubble_dew or pcs_gc_bubble_dew_temperature returned.  Both entry points launch one kernel
+ * template (csrc/gc_incipient.hip); pcs_gc_jacobian is this call with jac_y = NULL.
+ *   jac_p [n,7]  out  d p / d (A00, A01, A11, B00, B01, B11, T), Pa per unit: pcs_gc_jacobian's jac, bit for bit, whether or
+ *                     not jac_y is requested (tests/golden/gc_jacobian_bits.json pins the bits) (optional)
  *   jac_y [n,7]  out  d y / d (the same 7), y = the mole fraction of COMPONENT 1 in the incipient phase -- the vapour for
  *                     bubble, y = rhoV_1 / (rhoV_1 + rhoV_2), the liquid for dew, y = rhoL_1 / (rhoL_1 + rhoL_2) -- at fixed
  *                     composition of the specified phase (optional)

@@ -4,7 +4,9 @@
 Compiles every translation unit of feos_torch_amd/build.py's SOURCES in both trees with that tree's own flags for the
 unit + --cuda-device-only -S (as isa_count.sh does) and prints, per device function, whether the instruction text and
 the kernel descriptor are identical.  A plain text comparison: the __hip_cuid_* lines, .file, .ident and comment lines
-are dropped, nothing else is interpreted.  Exit status 1 if any function differs or exists in one tree only.
+are dropped, and local labels lose the ordinal of their function within the unit (.LBB<k>_<n> -> .LBB_<n>: a function
+removed from or added to a unit renumbers all that follow it); nothing else is interpreted.  Exit status 1 if any function
+differs or exists in one tree only.
 """
 import argparse
 import importlib.util
@@ -39,6 +41,7 @@ def functions(path):
         s = raw.split(";")[0].strip()  # comments, at the start of a line or behind an instruction, carry no code
         if not s or s.startswith("//") or "__hip_cuid_" in s or s.startswith(".file") or s.startswith(".ident"):
             continue
+        s = re.sub(r"\.L(BB|JTI)\d+_", r".L\1_", s)
         m = re.match(r"^\.type\s+(\S+),@function", s)
         if m:
             cur = out.setdefault(m.group(1), [False, [], []])

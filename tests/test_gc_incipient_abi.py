@@ -34,8 +34,9 @@ def test_kernel_resources(hip_lib):
         # held to the default limit: none of the relaxed name patterns of tests/test_abi.py applies
         assert "vjp" not in k and "k_gc_segment_gradient<1," not in k and "k_mixn" not in k, k
         assert res[k]["scratch"] <= 2304, (k, res[k])
-    # the default backward passes are still there
-    assert "k_gc_jacobian" in res and any("k_gc_segment_gradient<0," in k for k in res)
+    # what serves the default backward passes: pcs_gc_jacobian launches the pressure-only instantiation (no kernel of its own)
+    assert "k_gc_jacobian" not in res and any("k_gc_point_jacobian<true, false>" in k for k in res)
+    assert any("k_gc_segment_gradient<0," in k for k in res)
     assert "gc_incipient.hip" in build.GUARDED_SOURCES and "gc_incipient.hip" not in build.RELAXED_SOURCES
     assert "gc_gradient.hip" not in build.GUARDED_SOURCES and "gc_gradient.hip" not in build.RELAXED_SOURCES
 

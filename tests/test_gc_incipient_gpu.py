@@ -226,6 +226,10 @@ def test_values_of_the_temperature_calls(oracle, hip_lib, dew):
 
 @pytest.mark.parametrize("dew", PROBLEMS)
 def test_jac_p_and_agg_have_the_bits_of_pcs_gc_jacobian(ctx, dew):
+    """The pressure block does not depend on whether the composition block is asked for, nor on the entry point.
+    pcs_gc_jacobian and pcs_gc_point_jacobian share one kernel template now (pcs_gc_jacobian launches <true, false>), so the
+    only_p line compares a kernel with itself; what it stood for, the bits of the kernel pcs_gc_jacobian used to have, is
+    held by tests/test_gc_jacobian_bits_gpu.py."""
     from feos_torch_amd import native
 
     g = ctx[dew]

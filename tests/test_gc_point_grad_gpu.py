@@ -1,7 +1,7 @@
 """GPU: the two kernels behind the gradient of GcPcSaftMix.bubble_point / dew_point against an exact long-double referee, class
 by class, and the launch geometry of the segment-gradient kernel's bubble / dew mode.
 
-  pcs_gc_jacobian (k_gc_jacobian)                          jac [n,7] = dp/d(A00, A01, A11, B00, B01, B11, T), agg [n,6]; chained
+  pcs_gc_jacobian (k_gc_point_jacobian<true, false>)       jac [n,7] = dp/d(A00, A01, A11, B00, B01, B11, T), agg [n,6]; chained
                                                            to k_ab, phi and T by gc_pcsaft._kab_gradient / _phi_gradient
   pcs_gc_segment_gradient (k_gc_segment_gradient<0, 192>)  grad_seg [S,8] += sum_i g_i dp_i/d segment table
 
@@ -337,7 +337,7 @@ def test_table_size_does_not_change_the_point_gradient(amd, oracle, name, dew):
 
     LDS of k_gc_segment_gradient<0, BLOCK>: 24 S^2 + 128 S + 704 BLOCK bytes.  BLOCK = 192 for every S (256 needs 180 224 B
     before the table): S = 6: 136 800 B, S = 23: 150 808 B, S = 32: 163 840 B -- exactly the LDS of a CU, accepted by the `<=`
-    of launch_gc_gradient_mode and by the runtime.  k_gc_jacobian (BLOCK 256, 24 S^2 + 64 S + 120 832 B) takes 147 456 B at S = 32;
+    of launch_gc_gradient_mode and by the runtime.  k_gc_point_jacobian (BLOCK 256,24 S^2 + 64 S + 120 832 B) takes 147 456 B at S = 32;
     neither kernel nor the solver had run at S = 32.  What the tables change is the LDS layout and the segment indices, not the
     result: status is equal, p, rho4, jac and agg agree with the full table to 1e-12 relative, the grad_seg rows of the shared
     segments to 1e-12 of the column scale, and the rows of unused and padded segments are exactly 0.
