@@ -482,6 +482,26 @@ def mix_derivatives(params, kij, temperature, density):
     return a, p, mu, v
 
 
+def mix_density(params, kij, temperature, pressure, molefracs, phase):
+    """Density root of binary mixtures at (T [K], p [Pa], x = mole fraction of component 1), phase 0 = liquid, 1 = vapour
+    (pcs_mix_density).  -> dict(rho [n] total density A^-3, dpdrho [n] reduced dp/drho along x at the root, status bool,
+    iters int32 evaluations, -1 for failed rows); outputs of failed rows are 0."""
+    if phase not in (0, 1):
+        raise ValueError("phase must be 0 (liquid) or 1 (vapour)")
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature, pressure, molefracs = _prep(temperature, device), _prep(pressure, device), _prep(molefracs, device)
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij, pressure=pressure, molefracs=molefracs)
+    rho, dpdrho = _news(device, n, n)
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32)
+    # no workspace: the entry point accepts the batch-wide class order and does not use it (include/pcsaft_hip.h)
+    _call(device, "pcs_mix_density", int(phase), params, kij, temperature, pressure, molefracs, n, rho, dpdrho, status, iters, None)
+    return {"rho": rho, "dpdrho": dpdrho, "status": status.view(torch.bool), "iters": iters}
+
+
 def mix_stability(params, kij, temperature, density):
     """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
     density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,

@@ -107,6 +107,51 @@ class _BubbleDew(torch.autograd.Function):
         return (None, *_shell.scatter(ctx.comp, jac, g, _COLUMNS, ctx.needs, ctx.in_devices), None, None, None, None, None)
 
 
+class _MixDensity(torch.autograd.Function):
+    """rho [n_ok, kmol/m3], nans [n], plan = liquid (phase 0) / vapour (phase 1) density at (T, p, x) in one kernel
+    (csrc/mix_density.hip), compacted like _BubbleDew.  Gradient to all five inputs by the implicit-function theorem on
+    p_model(theta, T, rho x) = p [Pa] 1e-30 / (k_B T): ONE pcs_mix_derivatives_vjp call at the root with the per-row weight
+    g_p = -g c / (dp/drho) (c = the unit factor), G [n_ok, 21]:
+        parameters, kij: G[:, :18];  T: G[:, 18] + g_p p_spec / T (the specified reduced pressure depends on T itself);
+        p: -g_p 1e-30 / (k_B T);  x: rho (G[:, 19] - G[:, 20])."""
+
+    COLUMNS = ((0, 16, (-1, 2, 8)), (16, 2, (-1, 2)), (18, 1, (-1,)), (19, 1, (-1,)), (20, 1, (-1,)))  # of the packed gradient [n_ok,21]
+    C = 1.0 / (1e3 * (6.02214076e23 * (1e-10 * 1e-10 * 1e-10)))  # A^-3 -> kmol/m3: 1 / RHO_UNIT of csrc/pcsaft_consts.hpp, as PcSaftPure.liquid_density
+    P_RED = 1e-30 / 1.380649e-23            # p_spec = p [Pa] P_RED / T
+
+    @staticmethod
+    def forward(ctx, phase, parameters, kij, temperature, pressure, molefracs):
+        dev = native._device_of(parameters)
+        par = native._prep(parameters, dev, (2, 8))
+        k = native._prep(kij, dev, (2,))
+        T, p, x = native._prep(temperature, dev), native._prep(pressure, dev), native._prep(molefracs, dev)
+        r = native.mix_density(par, k, T, p, x, phase)
+        comp = native.Compaction(r["status"])
+        rho = comp.gather(r["rho"])
+        ctx.needs = list(ctx.needs_input_grad[1:6])
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs):
+            x_ok = comp.gather(x)
+            ctx.save_for_backward(comp.gather(par), comp.gather(k), comp.gather(T), torch.stack((x_ok * rho, (1.0 - x_ok) * rho), dim=1),
+                                  comp.gather(r["dpdrho"]), comp.gather(p))
+            ctx.comp = comp
+        ctx.in_devices = tuple(t.device for t in (parameters, kij, temperature, pressure, molefracs))
+        return (*_shell.finish(ctx, parameters.device, [rho * _MixDensity.C], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        if g is None:
+            return (None,) * 6
+        par, k, T, rho2, dpdrho, p = ctx.saved_tensors
+        w = -(g.to(T.device) * _MixDensity.C) / dpdrho  # g_p
+        G = native.mix_derivatives_vjp(par, k, T, rho2, g_p=w)
+        unit = _MixDensity.P_RED / T
+        packed = torch.cat((G[:, :18], (G[:, 18] + w * p * unit / T)[:, None], (-w * unit)[:, None],
+                            ((rho2[:, 0] + rho2[:, 1]) * (G[:, 19] - G[:, 20]))[:, None]), dim=1)
+        return (None, *_shell.scatter(ctx.comp, packed, None, _MixDensity.COLUMNS, ctx.needs, ctx.in_devices))
+
+
 class _MixDerivatives(torch.autograd.Function):
     """(a, p, mu, v) = derivatives(parameters[n,2,8], kij[n,2], temperature[n], density[n,2]) with gradients to all four
     inputs (feos_torch/pcsaft_mix.py:31-154, :395-420 are torch graphs in the reference)."""
@@ -260,6 +305,33 @@ class PcSaftMix(_shell.Reducible):
         such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution.
         incipient_molefracs=True: a last element x, the mole fraction of component 1 in the incipient liquid."""
         return self._point(True, True, pressure, vapor_molefracs, temperature, check_stability, incipient_molefracs)
+
+    def _density(self, phase, temperature, pressure, molefracs):
+        if self.ncomp != 2:
+            raise Exception("liquid_density and vapor_density are implemented for binary mixtures")
+        as64 = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t, dtype=torch.float64)
+        rho, nans, comp = _MixDensity.apply(phase, self._par, self.kij, as64(temperature), as64(pressure), as64(molefracs))
+        self._reduce(comp)
+        return rho, nans
+
+    def liquid_density(self, temperature, pressure, liquid_molefracs):
+        """(rho [kmol/m3], nans): total molar density of the liquid at T [K], p [Pa] and the mole fraction of component 1 --
+        the tuple order of this class's bubble_point, (value, nans), not PcSaftPure.liquid_density's.  With eta the packing
+        fraction along the composition line: the largest root of p(rho) = p at or below eta = 0.5 that is reached from there
+        with dp/drho > 0 throughout, or, where the pressure at eta = 0.5 is below p, the first root above it (eta < 0.74) --
+        the liquid root of the bubble-point initialisation, converged to rounding (include/pcsaft_hip.h, pcs_mix_density).
+        Values for the converged rows only; the model is reduced like bubble_point does.  A row fails where T, p or x is not
+        finite, T <= 0, p <= 0, x outside [0, 1] (x = 0 and x = 1 are valid), or where the liquid branch ends (dp/drho = 0)
+        before it reaches p.  Differentiable w.r.t. parameters, kij, temperature, pressure and the mole fractions
+        (implicit-function theorem, one pcs_mix_derivatives_vjp call).  Not part of the reference's class."""
+        return self._density(0, temperature, pressure, liquid_molefracs)
+
+    def vapor_density(self, temperature, pressure, vapor_molefracs):
+        """(rho [kmol/m3], nans): total molar density of the vapour at T [K], p [Pa] and the mole fraction of component 1:
+        the smallest root of p(rho) = p, reached from the ideal gas with dp/drho > 0 throughout; a row fails where the
+        vapour branch ends below p (and for the invalid inputs of liquid_density).  Tuple order, reduction and gradients as
+        for liquid_density."""
+        return self._density(1, temperature, pressure, vapor_molefracs)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's

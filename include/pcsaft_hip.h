@@ -285,6 +285,47 @@ int pcs_mix_bubble_dew_temperature(int dew, const double* params, const double* 
                                    int32_t* iters, void* workspace, void* stream);
 
 /*
+ * Density of a binary mixture at given (T, p, x): the liquid-like (phase = 0) or the vapour-like (phase = 1) root of
+ * p(x rho, (1 - x) rho) = p_spec along the composition line, one kernel (csrc/mix_density.hpp), ABI 114.  Reduced units as for
+ * pcs_mix_derivatives; with a, a', a'' the Helmholtz energy density and its derivatives along the line rho_i = x_i rho,
+ *     p(rho) = rho - a + rho a',    dp/drho = 1 + rho a'',    p_spec = p [Pa] 1e-30 / (k_B T),    eta = packing(x) rho.
+ * The roots:
+ *   liquid, with rho_s = 0.5 / packing:
+ *     p(rho_s) >= p_spec: the largest rho <= rho_s with p(rho) = p_spec, provided dp/drho > 0 on all of [rho, rho_s]; if
+ *                         dp/drho reaches 0 first, the liquid branch ends above p_spec and the row fails;
+ *     p(rho_s) <  p_spec: the smallest rho > rho_s with p(rho) = p_spec, dp/drho > 0 and eta < 0.74; if there is none, the row
+ *                         fails.
+ *     This is the root the bubble-point initialisation takes (start at eta = 0.5, scaled Newton, first bracket above
+ *     eta = 0.5), converged to rounding.
+ *   vapour: the smallest rho > 0 with p(rho) = p_spec, provided dp/drho > 0 on (0, rho]; started at the ideal gas
+ *           rho = p_spec (at eta = 0.05 where the ideal gas is denser: far above the branch it lies at liquid densities); the
+ *           row fails if the branch ends first.
+ * Safeguarded Newton inside a bracket kept on the branch, bisection where a step leaves the bracket or dp/drho <= 0; the
+ * branch is walked from its start in steps of at most a factor 0.8 (down) / 1.25 (up) in density, 0.06 in eta above
+ * eta = 0.5, so that a step cannot reach the other branch.  Accepted: |d rho| <= 1e-14 rho, or a step that has stopped
+ * shrinking below 1e-12 rho (rounding floor); at most 64 evaluations per row.
+ *   params   [n,2,8] in   (16-byte aligned)
+ *   kij      [n,2]   in   (16-byte aligned) as for pcs_mix_bubble_dew
+ *   temp     [n]     in   K
+ *   pressure [n]     in   Pa
+ *   x        [n]     in   mole fraction of component 1, 0 <= x <= 1 (both ends are valid)
+ *   rho      [n]     out  A^-3, the total density                                     (optional)
+ *   dpdrho   [n]     out  the reduced dp/drho along x at the root (> 0)                (optional)
+ *   status   [n]     out  uint8, 1 = failed; outputs of such rows are 0.  A row fails AT ONCE when T, p or x is non-finite,
+ *                         T <= 0, p <= 0 or x outside [0, 1]; otherwise by the root definitions above, where an evaluation is
+ *                         not finite, or at the cap
+ *   iters    [n]     out  int32 evaluations used, -1 for failed rows (optional)
+ *   workspace             optional, pcs_workspace_bytes(n): the batch-wide class order of pcs_mix_derivatives_vjp.  Accepted
+ *                         and NOT used: the rows are taken in their own order (one row per lane, no work queue, no LDS)
+ * A row's result does not depend on the rows it shares a wave with.  Backward pass: G = pcs_mix_derivatives_vjp at
+ * (x rho, (1 - x) rho) with g_p = -g / dpdrho and no other weight:  d rho/d(params, kij) = G[:, :18],
+ * d rho/dT = G[:, 18] + g_p p_spec / T,  d rho/dp [Pa] = -g_p 1e-30 / (k_B T),  d rho/dx = rho (G[:, 19] - G[:, 20]).
+ */
+int pcs_mix_density(int phase, const double* params, const double* kij, const double* temp, const double* pressure,
+                    const double* x, int64_t n, double* rho, double* dpdrho, uint8_t* status, int32_t* iters,
+                    void* workspace, void* stream);
+
+/*
  * PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420) at given partial densities rho [n,2]:
  * a [n], p [n] (reduced), residual chemical potentials mu [n,2], partial molar volumes v [n,2].
  * Any output may be NULL.

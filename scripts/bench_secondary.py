@@ -24,6 +24,10 @@ with HIP events on the launch stream, inputs resident in HBM.
             pcs_gc_jacobian next to pcs_gc_point_jacobian (pressure block only, composition block only, both) and
             pcs_gc_segment_gradient next to pcs_gc_point_segment_gradient (gout_p only, gout_y only, both); the comparison is
             against the parent kernels run in the same process
+  density: PcSaftMix.liquid_density / vapor_density kernel (pcs_mix_density) on mix_batch(1e6) at 3 x the bubble pressure
+            (liquid) / 0.5 x the dew pressure (vapour) of the same process's bubble_point / dew_point (1e5 Pa where those fail);
+            pcs_mix_derivatives and the bubble / dew solve alongside, forward + backward through the model class, failed rows
+            and the histogram of evaluations per row
 Prints one JSON object per config."""
 import json
 import os
@@ -301,3 +305,30 @@ if "gc_incipient" in which:
                           "jacobian_both_over_two_gc_jacobian": ms["point_jacobian_both"] / (2.0 * ms["gc_jacobian"]),
                           "segment_both_over_two_single": ms["point_segment_gradient_both"] / (ms["point_segment_gradient_p"] + ms["point_segment_gradient_y"]),
                           "segment_both_over_two_segment_gradient": ms["point_segment_gradient_both"] / (2.0 * ms["segment_gradient"])}))
+if "density" in which:
+    # one row per lane in batch order, no work queue: a wave pays its slowest row.  The neighbours on the same rows: one state
+    # evaluation (pcs_mix_derivatives at the root) and the bubble / dew solve that gave the pressure
+    from feos_torch_amd import PcSaftMix
+    n = 1_000_000
+    P, K, T, X, PI = mix_batch(n)
+    a = [d(v) for v in (P, K, T, X, PI)]
+    for phase, factor in ((0, 3.0), (1, 0.5)):
+        ms_point, rp = timed(lambda: native.mix_bubble_dew(*a, bool(phase)), reps=3)
+        p = torch.where(rp["status"], torch.full_like(rp["p"], 1e5), factor * rp["p"]).contiguous()
+        ms, r = timed(lambda: native.mix_density(a[0], a[1], a[2], p, a[3], phase), reps=5)
+        ok = ~r["status"]
+        rho2 = torch.stack((a[3] * r["rho"], (1.0 - a[3]) * r["rho"]), dim=1).contiguous()
+        rho2[r["status"]] = 5e-3
+        ms_deriv, _ = timed(lambda: native.mix_derivatives(a[0], a[1], a[2], rho2), reps=5)
+
+        def fwd_bwd():
+            leaves = [v.clone().requires_grad_(True) for v in (a[0], a[1], a[2], p, a[3])]
+            m = PcSaftMix(leaves[0], leaves[1])
+            rho, _ = (m.vapor_density if phase else m.liquid_density)(*leaves[2:])
+            rho.sum().backward()
+            return leaves[0].grad
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        print(json.dumps({"config": f"PcSaftMix {'vapor' if phase else 'liquid'}_density batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_mix_derivatives": ms_deriv, "ms_bubble_dew_point": ms_point, "ms_forward_backward": ms_fb,
+                          "failed": int(r["status"].sum()), "failed_point": int(rp["status"].sum()),
+                          "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
