@@ -726,11 +726,9 @@ static int launch_gc_gradient(int mode, const GcGradArgs& a, void* stream, const
 int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                             const double* rho4, int64_t n, const double* gout, double* grad_seg, const int32_t* order,
                             void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho4 || !grad_seg) return fail_msg("pcs_gc_segment_gradient: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_segment_gradient: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && rho4 && grad_seg, "pcs_gc_segment_gradient: null required pointer"); e != GO_ON)
+        return e;
+    if (int e = aligned16("pcs_gc_segment_gradient", "rows", rows)) return e;
     GcGradArgs a{};
     a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
     a.gout = gout; a.grad_seg = grad_seg; a.order = order;
@@ -747,7 +745,7 @@ int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uin
     if (!table || !rows || !phi || !temp || !rho4 || !grad_seg)
         return fail_msg("pcs_gc_point_segment_gradient", "null required pointer (table, rows, phi, temp, rho4, grad_seg)");
     if (!gout_p && !gout_y) return fail_msg("pcs_gc_point_segment_gradient", "gout_p and gout_y are both null (one weight vector is required)");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_point_segment_gradient", "rows must be 16-byte aligned");
+    if (int e = aligned16("pcs_gc_point_segment_gradient", "rows", rows)) return e;
     GcGradArgs a{};
     a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
     a.gout = gout_p; a.gout_y = gout_y; a.grad_seg = grad_seg; a.order = order;
@@ -757,11 +755,9 @@ int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uin
 int pcs_gc_derivatives_vjp(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                            const double* rho, int64_t n, const double* g_a, const double* g_p, const double* g_mu,
                            const double* g_v, double* grad_seg, double* jac9, double* agg, const int32_t* order, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho || !grad_seg || !jac9) return fail_msg("pcs_gc_derivatives_vjp: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_derivatives_vjp: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && rho && grad_seg && jac9, "pcs_gc_derivatives_vjp: null required pointer"); e != GO_ON)
+        return e;
+    if (int e = aligned16("pcs_gc_derivatives_vjp", "rows", rows)) return e;
     GcGradArgs a{};
     a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho; a.n = n;
     a.g_a = g_a; a.g_p = g_p; a.g_mu = g_mu; a.g_v = g_v; a.grad_seg = grad_seg; a.jac9 = jac9; a.agg = agg; a.order = order;

@@ -240,11 +240,8 @@ extern "C" {
 
 int pcs_gc_jacobian(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                     const double* rho4, int64_t n, double* jac, double* agg, const int32_t* order, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho4 || !jac) return fail_msg("pcs_gc_jacobian: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_jacobian: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && rho4 && jac, "pcs_gc_jacobian: null required pointer"); e != GO_ON) return e;
+    if (int e = aligned16("pcs_gc_jacobian", "rows", rows)) return e;
     return launch_gc_point_jacobian(dew, table, S, rows, phi, temp, rho4, n, jac, nullptr, agg, order, stream);
 }
 
@@ -258,7 +255,7 @@ int pcs_gc_point_jacobian(int dew, const double* table, int S, const uint8_t* ro
     if (!table || !rows || !phi || !temp || !rho4)
         return fail_msg("pcs_gc_point_jacobian", "null required pointer (table, rows, phi, temp, rho4)");
     if (!jac_p && !jac_y) return fail_msg("pcs_gc_point_jacobian", "jac_p and jac_y are both null (one output is required)");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_point_jacobian", "rows must be 16-byte aligned");
+    if (int e = aligned16("pcs_gc_point_jacobian", "rows", rows)) return e;
     return launch_gc_point_jacobian(dew, table, S, rows, phi, temp, rho4, n, jac_p, jac_y, agg, order, stream);
 }
 

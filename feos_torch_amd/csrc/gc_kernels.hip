@@ -47,26 +47,7 @@ __global__ __launch_bounds__(GBLOCK) void k_gc_bubble_dew(const double* __restri
     m.c.bond_dab = bonds + threadIdx.x;
     m.c.stride = GBLOCK;
     int64_t first = (int64_t)blockIdx.x * GBLOCK + threadIdx.x;
-    if (!RETRY && order) {
-        // batch-wide class order from the caller (computed once per model: the rows are fixed): class-uniform waves.
-        // Measured with host-sorted rows: bubble 3.0 -> 2.1 ms, dew 7.8 -> 5.6 ms per 1e6 rows
-        const int64_t o = first < n ? (int64_t)order[first] : n;
-        first = (o >= 0 && o < n) ? o : n;  // a foreign order array must not fault
-    }
-    if (!RETRY && !order) {
-        // rows of the workgroup bucketed by class (LDS counting sort): lane t takes the row at sorted position t, so a
-        // wave mostly runs one set of branches of the evaluation
-        __shared__ int bins[GC_BINS + 1];
-        __shared__ int perm[GBLOCK];
-        const int t = threadIdx.x;
-        // rows past n sort last, in a bucket of their own
-        block_order<GC_BINS + 1>(bins, perm, [=] {
-            int key = GC_BINS;
-            if (first < n) key = gc_bucket(rows + (size_t)first * GC_ROW_BYTES, tb);
-            return key;
-        });
-        first = (int64_t)blockIdx.x * GBLOCK + perm[t];
-    }
+    if constexpr (!RETRY) first = gc_pick_row<GBLOCK>(rows, tb, n, order);  // class-uniform waves
     const int64_t total = RETRY ? min((int64_t)max(retry[0], 0), n) : n;  // count and entries bounded by n: a foreign list must not fault
     const int64_t stride = RETRY ? (int64_t)gridDim.x * GBLOCK : total;  // fast pass: one row per lane
     for (int64_t k = first; k < total; k += stride) {
@@ -158,11 +139,9 @@ int64_t pcs_gc_table_doubles(int S) { return (int64_t)S * 8 + 3 * (int64_t)S * S
 int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                       const double* z, const double* p_init, int64_t n, double* p_out, double* rho4, uint8_t* status,
                       int32_t* iters, const int32_t* order, void* workspace, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !z || !p_init || !status) return fail_msg("pcs_gc_bubble_dew: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_bubble_dew: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && z && p_init && status, "pcs_gc_bubble_dew: null required pointer"); e != GO_ON)
+        return e;
+    if (int e = aligned16("pcs_gc_bubble_dew", "rows", rows)) return e;
     const unsigned grid = grid_for(n, GBLOCK);
     const size_t lds = gc_lds_bytes(S, GBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES);
     hipStream_t s = as_stream(stream);
@@ -177,11 +156,8 @@ int pcs_gc_bubble_dew(int dew, const double* table, int S, const uint8_t* rows, 
 
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho) return fail_msg("pcs_gc_derivatives: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_derivatives: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && rho, "pcs_gc_derivatives: null required pointer"); e != GO_ON) return e;
+    if (int e = aligned16("pcs_gc_derivatives", "rows", rows)) return e;
     const unsigned grid = grid_for(n, GBLOCK);
     hipLaunchKernelGGL(k_gc_derivatives, dim3(grid), dim3(GBLOCK), gc_lds_bytes(S, GBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES), as_stream(stream),
                        table, S, rows, phi, temp, rho, n, a, p, mu, v);

@@ -39,23 +39,7 @@ __global__ __launch_bounds__(GTBLOCK) void k_gc_temperature(const double* __rest
     double* bonds = lds + gc_table_doubles(S);          // [2*MAXE][GTBLOCK]: the bond diameters d_ab
     double* row_area = bonds + 2 * GC_MAXE * GTBLOCK;   // the lanes' row bytes (stage_row)
     const int t = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * GTBLOCK;
-    int64_t i = row0 + t;
-    if (order) {
-        // batch-wide class order from the caller (see k_gc_bubble_dew); a foreign order array must not fault
-        const int64_t o = i < n ? (int64_t)order[i] : n;
-        i = (o >= 0 && o < n) ? o : n;
-    } else {
-        // rows of the workgroup bucketed by class; rows past n sort last, in a bucket of their own
-        __shared__ int bins[GC_BINS + 1];
-        __shared__ int perm[GTBLOCK];
-        block_order<GC_BINS + 1>(bins, perm, [=] {
-            int key = GC_BINS;
-            if (i < n) key = gc_bucket(rows + (size_t)i * GC_ROW_BYTES, tb);
-            return key;
-        });
-        i = row0 + perm[t];
-    }
+    const int64_t i = gc_pick_row<GTBLOCK>(rows, tb, n, order);
     if (i >= n) return;  // (behind every barrier of the kernel)
     const unsigned char* row = stage_row(rows + (size_t)i * GC_ROW_BYTES, row_area);
     double ph0 = phi[2 * i], ph1 = phi[2 * i + 1], zz = z[i];
@@ -93,9 +77,7 @@ extern "C" {
 int pcs_gc_bubble_dew_temperature(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* p_spec,
                                   const double* z, const double* t_init, int64_t n, double* t_out, double* rho4, uint8_t* status,
                                   int32_t* iters, const int32_t* order, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (int e = enter(n, table && rows && phi && p_spec && z && t_init && status, "pcs_gc_bubble_dew_temperature: null required pointer");
+    if (int e = gc_enter(S, n, table && rows && phi && p_spec && z && t_init && status, "pcs_gc_bubble_dew_temperature: null required pointer");
         e != GO_ON)
         return e;
     if (int e = aligned16("pcs_gc_bubble_dew_temperature", "rows and rho4", rows, rho4)) return e;

@@ -33,18 +33,8 @@ __global__ __launch_bounds__(MBLOCK) void k_mix_point_jacobian(int dew, const do
     __shared__ int bins[MIX_BINS + 1];
     __shared__ double adj_lds[ADJ_SLOTS * MBLOCK];  // coefficient adjoints of this lane's row: adj_lds[k * MBLOCK + t]
     const int t = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * MBLOCK;
-    int64_t i;
-    if (order) {
-        if (row0 + t >= n) return;
-        i = order[row0 + t];
-        if (i < 0 || i >= n) return;
-    } else {
-        // rows past n sort last, in a bucket of their own
-        block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
-        i = row0 + perm[t];
-        if (i >= n) return;
-    }
+    const int64_t i = mix_pick_row<MBLOCK>(params, n, order, bins, perm);
+    if (i >= n) return;
     double par[16], k0, k1;
     load_mix_row(params, kij, i, par, k0, k1);
     const double4 r = reinterpret_cast<const double4*>(rho4)[i];  // (V0, V1, L0, L1)
@@ -64,11 +54,8 @@ int pcs_mix_point_jacobian(int dew, const double* params, const double* kij, con
     if (int e = enter(n, params && kij && temp && rho4, "pcs_mix_point_jacobian: null required pointer"); e != GO_ON) return e;
     if (!jac_p && !jac_y) return fail_msg("pcs_mix_point_jacobian", "jac_p and jac_y are both null (one output is required)");
     hipStream_t s = as_stream(stream);
-    const int32_t* order = nullptr;
-    if (workspace) {  // batch-wide class order (the permutation of the work-queue schedule)
-        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
-        order = static_cast<const int32_t*>(workspace);
-    }
+    const int32_t* order;  // batch-wide class order (the permutation of the work-queue schedule)
+    if (int e = mix_class_order(params, n, workspace, s, order)) return e;
     hipLaunchKernelGGL(k_mix_point_jacobian, dim3(grid_for(n, MBLOCK)), dim3(MBLOCK), 0, s, dew, params, kij, temp, rho4, n,
                        jac_p, jac_y, order);
     return launched("k_mix_point_jacobian launch");

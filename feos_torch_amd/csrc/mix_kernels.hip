@@ -39,16 +39,9 @@ __global__ __launch_bounds__(MBLOCK, 1) void k_mix_bubble_dew(const double* __re
                                                            const double* __restrict__ p_init, int64_t n,
                                                            double* __restrict__ p_out, double* __restrict__ rho4,
                                                            uint8_t* __restrict__ status, int32_t* __restrict__ iters) {
-    // bucket the rows of the workgroup by association class and polarity (LDS counting sort) so the lanes of
-    // a wave mostly run the same branches of the Helmholtz energy: the cross-association site-fraction solve
-    // costs ~5x the rest of an evaluation and would otherwise be paid by every wave
     __shared__ int perm[MBLOCK];
     __shared__ int bins[MIX_BINS + 1];
-    const int t = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * MBLOCK;
-    // rows past n sort last, in a bucket of their own
-    block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
-    const int64_t i = row0 + perm[t];
+    const int64_t i = mix_pick_row<MBLOCK>(params, n, nullptr, bins, perm);  // bucketed by class inside the workgroup
     if (i >= n) return;
     double par[16], k0, k1;
     load_mix_row(params, kij, i, par, k0, k1);
@@ -135,9 +128,8 @@ __global__ __launch_bounds__(256) void k_mix_class_scatter(const double* __restr
 // state machine finds them with the full mixture evaluation at x = (1, 0) and (0, 1) -- 8-9 of a dew row's ~20 T2
 // evaluations, on the one-wave-per-SIMD queue kernel.  At those compositions the mixture model IS the pure-component
 // model (BMCSL -> Carnahan-Starling, g_ii -> (1 - eta/2)/(1 - eta)^3, one-fluid dispersion -> the pure sums, the dipole
-// quotient's pure limit, association of the component's own sites only), so the same Newton iteration -- same start,
-// same scaled function, same acceptance rule, same first-order carry of the chemical potential to the root as
-// BdLane::consume (S_ROOT, plain form) -- runs here on the closed-form pure evaluation (pure_a<double, D2>, ~350
+// quotient's pure limit, association of the component's own sites only), so the same Newton iteration (PureLiquidRoot,
+// mix_solver_sm.hpp) runs here on the closed-form pure evaluation (pure_a<double, D2>, ~350
 // instructions instead of 1,600-3,500), one (row, component) per lane, four waves per SIMD.  Results agree with the
 // state machine's to rounding; a lane the plain form would give up on writes NaN and the row takes the state machine's own
 // route (including its robust second attempt), so no decision of the solver changes.
@@ -173,47 +165,18 @@ __global__ __launch_bounds__(256) void k_mix_pure_fugacity(const double* __restr
     if (!self_i) { par[6] = 0.0; par[7] = 0.0; }
     PureCoef<double> c;
     pure_coef<double>(c, par, T, false);
-    const double pk = c.ceta;
-    double rho = 0.5 / pk, err_prev = 1.0, f = __longlong_as_double(0x7ff8000000000000LL), rho_root = 0.0;
-    bool dense = false, active = live && usable;
-    int it = 0;
+    PureLiquidRoot r;
+    r.start(c.ceta, live && usable);
     for (int guard = 0; guard < LIQ_ROOT_MAX_IT + 2; guard++) {
-        if (active) {
-            const D2<double> a = pure_a<double, D2<double>>(c, D2<double>(rho, 1.0, 0.0));
-            const double p = rho - a.v + rho * a.d1, dp = 1.0 + rho * a.d2;
-            if (it == 0 && !dense && !(p > 0.0)) {
-                rho = 0.62 / pk;  // very cold / dense: restart on the dense side (BdLane::consume)
-                dense = true;
-            } else {
-                const double den = dense ? dp : dp - 4.0 * p * pk / (1.0 - rho * pk);
-                bool bad = !(dp > 0.0) || !(den > 0.0) || !is_finite_bits(p);
-                const double step = p / den, rho_new = rho - step;
-                bad = bad || !(rho_new > 0.0) || !is_finite_bits(rho_new);
-                bad = bad || (dense && !(rho_new * pk > 0.5 && rho_new * pk < 0.62));
-                bool done = false;
-                if (!bad) {
-                    const double err = fabs(step) / rho;
-                    done = err <= LIQ_ROOT_TOL || (it >= 3 && err < 1e-7 && err >= 0.25 * err_prev);
-                    err_prev = err;
-                    it++;
-                    if (!done && it >= LIQ_ROOT_MAX_IT) bad = true;
-                }
-                if (bad) {
-                    active = false;  // NaN: the state machine decides (robust second attempt)
-                } else if (done) {
-                    f = rho_new * exp(a.d1 - a.d2 * step);  // chemical potential carried to the root to first order
-                    rho_root = rho_new;
-                    active = false;
-                } else {
-                    rho = rho_new;
-                }
-            }
+        if (r.active) {
+            const D2<double> a = pure_a<double, D2<double>>(c, D2<double>(r.rho, 1.0, 0.0));
+            r.step(r.rho - a.v + r.rho * a.d1, 1.0 + r.rho * a.d2, a.d1, a.d2);
         }
-        if (__ballot(active) == 0ull) break;
+        if (__ballot(r.active) == 0ull) break;
     }
     if (live) {
-        fug[4 * pos + comp] = f;
-        fug[4 * pos + 2 + comp] = rho_root;
+        fug[4 * pos + comp] = r.f;
+        fug[4 * pos + 2 + comp] = r.root;
     }
 }
 
@@ -509,18 +472,8 @@ __global__ __launch_bounds__(MBLOCK) void k_mix_jacobian(int dew, const double* 
     __shared__ int bins[MIX_BINS + 1];
     __shared__ double adj_lds[ADJ_SLOTS * MBLOCK];  // coefficient adjoints of this lane's row: adj_lds[k * MBLOCK + t]
     const int t = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * MBLOCK;
-    int64_t i;
-    if (order) {
-        if (row0 + t >= n) return;
-        i = order[row0 + t];
-        if (i < 0 || i >= n) return;
-    } else {
-        // rows past n sort last, in a bucket of their own
-        block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
-        i = row0 + perm[t];
-        if (i >= n) return;
-    }
+    const int64_t i = mix_pick_row<MBLOCK>(params, n, order, bins, perm);
+    if (i >= n) return;
     double par[16], k0, k1;
     load_mix_row(params, kij, i, par, k0, k1);
     double4 r = reinterpret_cast<const double4*>(rho4)[i];  // (V0, V1, L0, L1)
@@ -650,11 +603,8 @@ int pcs_mix_derivatives_vjp(const double* params, const double* kij, const doubl
                             void* workspace, void* stream) {
     if (int e = enter(n, params && kij && temp && rho && grad, "pcs_mix_derivatives_vjp: null required pointer"); e != GO_ON) return e;
     hipStream_t s = as_stream(stream);
-    const int32_t* order = nullptr;
-    if (workspace) {
-        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
-        order = static_cast<const int32_t*>(workspace);
-    }
+    const int32_t* order;
+    if (int e = mix_class_order(params, n, workspace, s, order)) return e;
     hipLaunchKernelGGL(k_mix_derivatives_vjp, dim3(grid_for(n, 64)), dim3(64), 0, s, params, kij, temp, rho, n, g_a,
                        g_p, g_mu, g_v, grad, order);
     return launched("k_mix_derivatives_vjp launch");
@@ -665,11 +615,8 @@ int pcs_mix_jacobian(int dew, const double* params, const double* kij, const dou
     if (int e = enter(n, params && kij && temp && rho4 && jac, "pcs_mix_jacobian: null required pointer"); e != GO_ON) return e;
     const unsigned grid = grid_for(n, MBLOCK);
     hipStream_t s = as_stream(stream);
-    const int32_t* order = nullptr;
-    if (workspace) {  // batch-wide class order (the permutation of the work-queue schedule)
-        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
-        order = static_cast<const int32_t*>(workspace);
-    }
+    const int32_t* order;  // batch-wide class order (the permutation of the work-queue schedule)
+    if (int e = mix_class_order(params, n, workspace, s, order)) return e;
     hipLaunchKernelGGL(k_mix_jacobian, dim3(grid), dim3(MBLOCK), 0, s, dew, params, kij, temp, rho4, n, jac, order);
     return launched("k_mix_jacobian launch");
 }

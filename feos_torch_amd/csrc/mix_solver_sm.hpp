@@ -244,8 +244,8 @@ struct BdLane {
                     if (!done && r_it >= 2 * LIQ_ROOT_MAX_IT) bad = true;
                 }
             } else {
-                // plain form.  Restated for a whole wave at p_spec = 0 by pure_fugacities_on_the_line (below) and k_mix_pure_fugacity
-                // (mix_kernels.hip) -- same start, scaled function, dense restart, acceptance rule: the three must change together
+                // plain form.  Restated at p_spec = 0 on a one-variable evaluation by PureLiquidRoot (below) -- same start, scaled
+                // function, dense restart, acceptance rule: the two must change together
                 if (r_it == 0 && !r_dense && !r_warm && !(p > r_pspec)) {
                     r_rho = 0.62 / r_pk;  // very cold / dense: restart on the dense side (plain Newton from there)
                     r_dense = true;
@@ -485,56 +485,71 @@ struct BdLane {
     }
 };
 
+// One lane's zero-pressure liquid root of a PURE component: the plain form's S_ROOT stage at p_spec = 0 (same start at
+// eta = 0.5, dense restart at 0.62, scaled Newton step, rejection list, acceptance rule and first-order carry of the chemical
+// potential to the root), on a ONE-variable evaluation a(rho) the caller provides: p = rho - a + rho a', dp = 1 + rho a''.
+// start(); while (active) { evaluate at rho; step(p, dp, a', a''); }.  A root the plain form would give up on leaves f = NaN,
+// root = 0 and the state machine takes its own route (robust second attempt).  f = rho_L exp(mu_res), root = rho_L.
+struct PureLiquidRoot {
+    double pk, rho, err_prev, f, root;
+    bool dense, active;
+    int it;
+    PCS_DEV void start(double packing, bool on) {
+        pk = packing;
+        rho = 0.5 / pk; err_prev = 1.0; f = __longlong_as_double(0x7ff8000000000000LL); root = 0.0;
+        dense = false; active = on;
+        it = 0;
+    }
+    PCS_DEV void step(double p, double dp, double d1, double d2) {
+        if (it == 0 && !dense && !(p > 0.0)) {
+            rho = 0.62 / pk;  // very cold / dense: restart on the dense side (BdLane::consume)
+            dense = true;
+            return;
+        }
+        const double den = dense ? dp : dp - 4.0 * p * pk / (1.0 - rho * pk);
+        bool bad = !(dp > 0.0) || !(den > 0.0) || !is_finite_bits(p);
+        const double step = p / den, rho_new = rho - step;
+        bad = bad || !(rho_new > 0.0) || !is_finite_bits(rho_new);
+        bad = bad || (dense && !(rho_new * pk > 0.5 && rho_new * pk < 0.62));
+        bool done = false;
+        if (!bad) {
+            const double err = fabs(step) / rho;
+            done = err <= LIQ_ROOT_TOL || (it >= 3 && err < 1e-7 && err >= 0.25 * err_prev);
+            err_prev = err;
+            it++;
+            if (!done && it >= LIQ_ROOT_MAX_IT) bad = true;
+        }
+        if (bad) {
+            active = false;  // NaN: the state machine decides
+        } else if (done) {
+            f = rho_new * exp(d1 - d2 * step);  // chemical potential carried to the root to first order
+            root = rho_new;
+            active = false;
+        } else {
+            rho = rho_new;
+        }
+    }
+};
+
 // Zero-pressure liquid fugacities of the two PURE components for Raoult's law (dew points), found on the ONE-variable
-// evaluation along each component's axis before the state machine starts -- the same Newton iteration as the plain form's
-// S_ROOT stage (same start, scaled function, dense restart, acceptance rule and first-order carry of the chemical potential
-// to the root), so the state machine continues exactly where it would have been, to rounding.  All lanes of the wave run
-// it together (the roots need 2-4 evaluations whatever the row).  A root the plain form would give up on leaves NaN, and
-// the state machine takes its own route (robust second attempt).  fug[i] = rho_L,i exp(mu_res,i), rho[i] = rho_L,i.
+// evaluation along each component's axis before the state machine starts (PureLiquidRoot), so the state machine continues
+// exactly where it would have been, to rounding.  All lanes of the wave run it together (the roots need 2-4 evaluations
+// whatever the row).  fug[i] = rho_L,i exp(mu_res,i), rho[i] = rho_L,i.
 template <class Model>
 PCS_DEV void pure_fugacities_on_the_line(const Model& m, double fug[2], double rho_root[2]) {
 #pragma unroll 1
     for (int comp = 0; comp < 2; comp++) {
         const double x0 = comp == 0 ? 1.0 : 0.0, x1 = 1.0 - x0;
-        const double pk = m.packing(x0, x1);
-        double rho = 0.5 / pk, err_prev = 1.0, f = __longlong_as_double(0x7ff8000000000000LL), rr = 0.0;
-        bool dense = false, active = true;
-        int it = 0;
+        PureLiquidRoot r;
+        r.start(m.packing(x0, x1), true);
         for (int guard = 0; guard < LIQ_ROOT_MAX_IT + 2; guard++) {
-            if (__ballot(active) == 0ull) break;
-            if (!active) continue;
-            const D2<double> a = line_eval(m, x0, x1, rho);
-            const double p = rho - a.v + rho * a.d1, dp = 1.0 + rho * a.d2;
-            if (it == 0 && !dense && !(p > 0.0)) {
-                rho = 0.62 / pk;
-                dense = true;
-                continue;
-            }
-            const double den = dense ? dp : dp - 4.0 * p * pk / (1.0 - rho * pk);
-            bool bad = !(dp > 0.0) || !(den > 0.0) || !is_finite_bits(p);
-            const double step = p / den, rho_new = rho - step;
-            bad = bad || !(rho_new > 0.0) || !is_finite_bits(rho_new);
-            bad = bad || (dense && !(rho_new * pk > 0.5 && rho_new * pk < 0.62));
-            bool done = false;
-            if (!bad) {
-                const double err = fabs(step) / rho;
-                done = err <= LIQ_ROOT_TOL || (it >= 3 && err < 1e-7 && err >= 0.25 * err_prev);
-                err_prev = err;
-                it++;
-                if (!done && it >= LIQ_ROOT_MAX_IT) bad = true;
-            }
-            if (bad) {
-                active = false;
-            } else if (done) {
-                f = rho_new * exp(a.d1 - a.d2 * step);
-                rr = rho_new;
-                active = false;
-            } else {
-                rho = rho_new;
-            }
+            if (__ballot(r.active) == 0ull) break;
+            if (!r.active) continue;
+            const D2<double> a = line_eval(m, x0, x1, r.rho);
+            r.step(r.rho - a.v + r.rho * a.d1, 1.0 + r.rho * a.d2, a.d1, a.d2);
         }
-        fug[comp] = f;
-        rho_root[comp] = rr;
+        fug[comp] = r.f;
+        rho_root[comp] = r.root;
     }
 }
 

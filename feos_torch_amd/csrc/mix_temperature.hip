@@ -90,11 +90,8 @@ int pcs_mix_bubble_dew_temperature(int dew, const double* params, const double* 
         return e;
     if (int e = aligned16("pcs_mix_bubble_dew_temperature", "params, kij and rho4", params, kij, rho4)) return e;
     hipStream_t s = as_stream(stream);
-    const int32_t* order = nullptr;
-    if (workspace) {  // batch-wide class order (the permutation of the work-queue schedule): class-uniform waves
-        if (int e = launch_mix_class_order(params, n, workspace, s)) return e;
-        order = static_cast<const int32_t*>(workspace);
-    }
+    const int32_t* order;  // batch-wide class order (the permutation of the work-queue schedule): class-uniform waves
+    if (int e = mix_class_order(params, n, workspace, s, order)) return e;
     const dim3 grid(grid_for(n, MBLOCK)), block(MBLOCK);
     if (dew) hipLaunchKernelGGL(k_mix_temperature<true>, grid, block, 0, s, params, kij, p_spec, z, t_init, n, t_out, rho4, status, iters, order);
     else hipLaunchKernelGGL(k_mix_temperature<false>, grid, block, 0, s, params, kij, p_spec, z, t_init, n, t_out, rho4, status, iters, order);

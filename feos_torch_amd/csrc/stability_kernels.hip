@@ -33,11 +33,7 @@ __global__ __launch_bounds__(SBLOCK) void k_mix_stability(const double* __restri
     // branches of the evaluation
     __shared__ int perm[SBLOCK];
     __shared__ int bins[MIX_BINS + 1];
-    const int t = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * SBLOCK;
-    // rows past n sort last, in a bucket of their own
-    block_order<MIX_BINS + 1>(bins, perm, [=] { return row0 + t < n ? mix_bucket(params + 16 * (row0 + t)) : MIX_BINS; });
-    const int64_t i = row0 + perm[t];
+    const int64_t i = mix_pick_row<SBLOCK>(params, n, nullptr, bins, perm);
     if (i >= n) return;
     double par[16], k0, k1;
     load_mix_row(params, kij, i, par, k0, k1);
@@ -85,11 +81,8 @@ int pcs_mix_stability(const double* params, const double* kij, const double* tem
 
 int pcs_gc_stability(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp, const double* rho,
                      int64_t n, double* tpd, double* rho_trial, uint8_t* status, const int32_t* order, void* stream) {
-    g_err[0] = 0;
-    if (int e = gc_check(S, n)) return e;
-    if (n == 0) return 0;
-    if (!table || !rows || !phi || !temp || !rho || !status) return fail_msg("pcs_gc_stability: null required pointer");
-    if (reinterpret_cast<uintptr_t>(rows) & 15) return fail_msg("pcs_gc_stability: rows must be 16-byte aligned");
+    if (int e = gc_enter(S, n, table && rows && phi && temp && rho && status, "pcs_gc_stability: null required pointer"); e != GO_ON) return e;
+    if (int e = aligned16("pcs_gc_stability", "rows", rows)) return e;
     const unsigned grid = grid_for(n, SBLOCK);
     hipLaunchKernelGGL(k_gc_stability, dim3(grid), dim3(SBLOCK), gc_lds_bytes(S, SBLOCK, 2 * GC_MAXE + GC_ROW_LDS_DOUBLES),
                        as_stream(stream), table, S, rows, phi, temp, rho, n, tpd, rho_trial, status, order);
