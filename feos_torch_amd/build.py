@@ -30,7 +30,10 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_C
            ("gc_incipient.hip", "gc_incipient.o", []),
            # liquid / vapour densities of binary mixtures at (T, p, x): guarded like mix_kernels.hip (the evaluation is
            # pcs_mix_derivatives' along the composition line), csrc/mix_density.hpp
-           ("mix_density.hip", "mix_density.o", [])]
+           ("mix_density.hip", "mix_density.o", []),
+           # liquid / vapour densities of gc rows at (T, p, x): guarded like gc_kernels.hip (the evaluation is pcs_gc_derivatives'
+           # along the composition line, the root is mix_density.hpp's), csrc/gc_density.hip
+           ("gc_density.hip", "gc_density.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,
@@ -63,7 +66,7 @@ RELAXED_SOURCES = {"pure_kernels.hip"}
 # results move by <= 6.4e-13 relative.  NaN / infinity semantics stay IEEE (no -fno-honor-*), which the failure detection needs.
 GUARDED = ["-DPCS_FAST_LOG=2", "-DPCS_FAST_RCP=2", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math"]
 GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip", "stability_kernels.hip", "mix_temperature.hip", "mix_incipient.hip", "gc_temperature.hip",
-                   "gc_incipient.hip", "mix_density.hip"}  # + the stability analysis (NaN / inf outcomes)
+                   "gc_incipient.hip", "mix_density.hip", "gc_density.hip"}  # + the stability analysis (NaN / inf outcomes)
 RESOURCES = os.path.join(HERE, "build", "resources.json")  # per-kernel register / stack report of the last build
 
 

@@ -319,6 +319,74 @@ class _GcBubbleDew(torch.autograd.Function):
         return (None, None, gk, gphi, ggiven, None, None, None, None, None, *gseg)
 
 
+class _GcDensity(torch.autograd.Function):
+    """rho [n_ok, kmol/m3], nans [n], plan = liquid (phase 0) / vapour (phase 1) density at (T, p, x) in one kernel
+    (csrc/gc_density.hip), compacted like _GcBubbleDew.  Gradient to every input by the implicit-function theorem on
+    p_model(theta, T, rho x) = p [Pa] 1e-30 / (k_B T): ONE pcs_gc_derivatives_vjp call at the root with the per-row weight
+    g_p = w = -g c / (dp/drho) (c = the unit factor) and no other weight -> grad_seg [S,8], jac9 [n_ok,9], agg [n_ok,6]:
+        segment vectors: the columns of grad_seg;  k_ab, phi: the pressure's own chains on jac9[:, :6];
+        T: jac9[:, 6] + w p_spec / T (the specified reduced pressure depends on T itself);  p: -w 1e-30 / (k_B T);
+        x: rho (jac9[:, 7] - jac9[:, 8]).
+    The class order is the model's (used by the solve; by the backward call only when no row was dropped)."""
+
+    C = 1.0 / (1e3 * (6.02214076e23 * (1e-10 * 1e-10 * 1e-10)))  # A^-3 -> kmol/m3, as _MixDensity.C
+    P_RED = 1e-30 / 1.380649e-23            # p_spec = p [Pa] P_RED / T
+
+    @staticmethod
+    def forward(ctx, phase, model, kab, phi, temperature, pressure, molefracs, *segment_parameters):
+        dev, S = model.device, model.S
+        table = _device_table(model.seg, kab, dev)
+        ph = native._prep(phi, dev, (2,))
+        T, p, x = native._prep(temperature, dev), native._prep(pressure, dev), native._prep(molefracs, dev)
+        order = _class_order(model, table)
+        r = native.gc_density(table, S, model.rows, ph, T, p, x, phase, order=order)
+        comp = native.Compaction(r["status"])
+        rho = comp.gather(r["rho"])
+        ctx.needs = list(ctx.needs_input_grad[2:7])  # k_ab, phi, temperature, pressure, molefracs
+        ctx.seg_needs = list(ctx.needs_input_grad[7:])
+        ctx.set_materialize_grads(False)
+        ctx.comp = None
+        if any(ctx.needs) or any(ctx.seg_needs):
+            x_ok = comp.gather(x)
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": comp.gather(T),
+                    "rho2": torch.stack((x_ok * rho, (1.0 - x_ok) * rho), dim=1), "dpdrho": comp.gather(r["dpdrho"]), "p": comp.gather(p)}
+            if comp.all_ok:  # the class order belongs to the uncompacted rows
+                keep["order"] = order
+            ctx.kept = tuple(keep)
+            ctx.save_for_backward(*keep.values())
+            ctx.comp = comp
+        ctx.S = S
+        ctx.seg_devs = [q.device for q in segment_parameters]
+        ctx.devs = tuple(t.device for t in (kab, phi, temperature, pressure, molefracs))
+        return (*_shell.finish(ctx, phi.device, [rho * _GcDensity.C], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        nseg = len(ctx.seg_needs)
+        comp, S = ctx.comp, ctx.S
+        if g is None or comp is None:
+            return (None,) * (7 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T, rho2 = kept["table"], kept["rows"], kept["ph"], kept["T"], kept["rho2"]
+        w = -(g.to(table.device) * _GcDensity.C) / kept["dpdrho"]  # g_p
+        gseg, jac9, agg = native.gc_derivatives_vjp(table, S, rows, ph, T, rho2, g_p=w, order=kept.get("order"))
+        unit = _GcDensity.P_RED / T
+        gk = gphi = gT = gp = gx = None
+        if ctx.needs[0]:
+            gk = _kab_gradient(table, S, rows, ph, T, jac9[:, 1], jac9[:, 4]).to(ctx.devs[0])
+        if ctx.needs[1]:
+            gphi = comp.expand(_phi_gradient(jac9, agg, ph)).to(ctx.devs[1])
+        if ctx.needs[2]:
+            gT = comp.expand(jac9[:, 6] + w * kept["p"] * unit / T).view(comp.n).to(ctx.devs[2])
+        if ctx.needs[3]:
+            gp = comp.expand(-w * unit).view(comp.n).to(ctx.devs[3])
+        if ctx.needs[4]:
+            gx = comp.expand((rho2[:, 0] + rho2[:, 1]) * (jac9[:, 7] - jac9[:, 8])).view(comp.n).to(ctx.devs[4])
+        gs = [gseg[:, k].to(dev) if need else None for k, (dev, need) in enumerate(zip(ctx.seg_devs, ctx.seg_needs))]
+        return (None, None, gk, gphi, gT, gp, gx, *gs)
+
+
 class GcPcSaftMix(_shell.Reducible):
     def __init__(self, segment_identifier, parameter, segment_lists, bond_lists, binary_segment_records, phi=None):
         """Arguments as the reference (feos_torch/gc_pcsaft.py:14-22): segment identifiers [S], the
@@ -413,6 +481,31 @@ class GcPcSaftMix(_shell.Reducible):
         `pressure` [Pa] (see bubble_temperature).  The retrograde dew branch near a mixture critical point is not served:
         such rows fail.  check_stability=True: (T, nans, stable) with the stability of the vapour at the solution."""
         return self._point(True, True, pressure, vapor_molefracs, temperature, check_stability)
+
+    def _density(self, phase, temperature, pressure, molefracs):
+        as64 = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t, dtype=torch.float64)
+        rho, nans, comp = _GcDensity.apply(phase, self, self.kab, self.phi, as64(temperature), as64(pressure), as64(molefracs),
+                                           *self._segment_parameters)
+        self._reduce(comp)
+        return rho, nans
+
+    def liquid_density(self, temperature, pressure, liquid_molefracs):
+        """(rho [kmol/m3], nans): total molar density of the liquid at T [K], p [Pa] and the mole fraction of component 1, the
+        contract of PcSaftMix.liquid_density on the gc model: the largest root of p(rho) = p at or below the packing
+        fraction 0.5 that is reached from there with dp/drho > 0 throughout, or, where the pressure at 0.5 is below p, the first
+        root above it (below 0.74) -- in one kernel (include/pcsaft_hip.h, pcs_gc_density).  Values for the converged rows
+        only; the model is reduced like bubble_point does.  A row fails where T, p or x is not finite, T <= 0, p <= 0, x outside
+        [0, 1] (x = 0 and x = 1 are valid: a pure gc fluid), phi is not finite, or where the liquid branch ends (dp/drho = 0)
+        before it reaches p.  Differentiable w.r.t. the eight segment parameter vectors, k_ab, phi, temperature, pressure and
+        the mole fractions (implicit-function theorem, one pcs_gc_derivatives_vjp call).  Not part of the reference's class."""
+        return self._density(0, temperature, pressure, liquid_molefracs)
+
+    def vapor_density(self, temperature, pressure, vapor_molefracs):
+        """(rho [kmol/m3], nans): total molar density of the vapour at T [K], p [Pa] and the mole fraction of component 1: the
+        smallest root of p(rho) = p, reached from the ideal gas with dp/drho > 0 throughout; a row fails where the vapour
+        branch ends below p (and for the invalid inputs of liquid_density).  Tuple order, reduction and gradients as for
+        liquid_density."""
+        return self._density(1, temperature, pressure, vapor_molefracs)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction

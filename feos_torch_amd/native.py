@@ -704,6 +704,28 @@ def gc_derivatives(table, S, rows, phi, temperature, density):
     return a, p, mu, v
 
 
+def gc_density(table, S, rows, phi, temperature, pressure, molefracs, phase, order=None):
+    """Density root of gc rows at (T [K], p [Pa], x = mole fraction of component 1), phase 0 = liquid, 1 = vapour
+    (pcs_gc_density).  table / rows / order as for gc_bubble_dew (order None: rows bucketed by class inside each workgroup,
+    same results).  -> dict(rho [n] total density A^-3, dpdrho [n] reduced dp/drho along x at the root, status bool,
+    iters int32 evaluations, -1 for failed rows); outputs of failed rows are 0."""
+    if phase not in (0, 1):
+        raise ValueError("phase must be 0 (liquid) or 1 (vapour)")
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature, pressure, molefracs = _prep(temperature, device), _prep(pressure, device), _prep(molefracs, device)
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi, pressure=pressure, molefracs=molefracs)
+    _check_order(order, n, device)
+    rho, dpdrho = _news(device, n, n)
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32)
+    _call(device, "pcs_gc_density", int(phase), table, int(S), rows, phi, temperature, pressure, molefracs, n, rho, dpdrho, status,
+          iters, order)
+    return {"rho": rho, "dpdrho": dpdrho, "status": status.view(torch.bool), "iters": iters}
+
+
 def gc_stability(table, S, rows, phi, temperature, density, order=None):
     """mix_stability for gc rows (pcs_gc_stability); order: optional class order of the rows (gc_class_order), schedule
     only.  -> dict(tpd, rho_trial, status)."""

@@ -473,6 +473,34 @@ int pcs_gc_bubble_dew_temperature(int dew, const double* table, int S, const uin
                                   const double* p_spec, const double* z, const double* t_init, int64_t n, double* t_out,
                                   double* rho4, uint8_t* status, int32_t* iters, const int32_t* order, void* stream);
 
+/*
+ * Density of a gc-PC-SAFT row at given (T, p, x) (ABI 115): pcs_mix_density on the gc model, one kernel
+ * (csrc/gc_density.hip on density_root of csrc/mix_density.hpp, one code for both models).  Root definitions (liquid from
+ * eta = 0.5, vapour from the ideal gas, a row whose branch ends before it reaches p fails instead of returning the other
+ * branch's root), acceptance rule, the cap of 64 evaluations and the reduced units are those of pcs_mix_density, with
+ * eta = packing(x) rho, packing = pi/6 sum_i x_i sum_segments n m d^3.  The reference has no counterpart.
+ *   phase                 0 = liquid, 1 = vapour; anything else is an error return
+ *   table, S, rows, phi   in   as for pcs_gc_bubble_dew (rows 16-byte aligned)
+ *   temp     [n]     in   K
+ *   pressure [n]     in   Pa
+ *   x        [n]     in   mole fraction of component 1, 0 <= x <= 1 (both ends are valid: a pure gc fluid)
+ *   rho      [n]     out  A^-3, the total density                                     (optional)
+ *   dpdrho   [n]     out  the reduced dp/drho along x at the root (> 0)                (optional)
+ *   status   [n]     out  uint8, 1 = failed; outputs of such rows are 0.  A row fails AT ONCE when T, p or x is non-finite,
+ *                         T <= 0, p <= 0, x outside [0, 1] or phi is non-finite; otherwise by the root definitions, where an
+ *                         evaluation is not finite, or at the cap
+ *   iters    [n]     out  int32 evaluations used, -1 for failed rows (optional)
+ *   order    [n]     in   optional class order of the rows as for pcs_gc_bubble_dew (NULL: bucketed by class inside each
+ *                         workgroup); only the schedule changes, results are identical.  One row per lane, no work queue.
+ * A row's result does not depend on the rows it shares a wave with.  Backward pass: pcs_gc_derivatives_vjp at
+ * (x rho, (1 - x) rho) with g_p = w = -g / dpdrho and no other weight: grad_seg is the segment-table gradient, jac9[:, :6] feed
+ * the k_ab and phi chains of the pressure, and  d rho/dT = jac9[:, 6] + w p_spec / T,  d rho/dp [Pa] = -w 1e-30 / (k_B T),
+ * d rho/dx = rho (jac9[:, 7] - jac9[:, 8]).
+ */
+int pcs_gc_density(int phase, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                   const double* pressure, const double* x, int64_t n, double* rho, double* dpdrho, uint8_t* status,
+                   int32_t* iters, const int32_t* order, void* stream);
+
 /* GcPcSaftMix.derivatives (feos_torch/gc_pcsaft.py:443-468): a, p, mu [n,2], v [n,2] at rho [n,2]. */
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream);

@@ -28,6 +28,10 @@ with HIP events on the launch stream, inputs resident in HBM.
             (liquid) / 0.5 x the dew pressure (vapour) of the same process's bubble_point / dew_point (1e5 Pa where those fail);
             pcs_mix_derivatives and the bubble / dew solve alongside, forward + backward through the model class, failed rows
             and the histogram of evaluations per row
+  gc_density: GcPcSaftMix.liquid_density / vapor_density kernel (pcs_gc_density) on gc_batch(1e6) in class order at 3 x the
+            bubble pressure (liquid) / 0.5 x the dew pressure (vapour) of the same process's bubble_point / dew_point (1e5 Pa
+            where those fail); pcs_gc_derivatives and the bubble / dew solve alongside, the same kernel without the class
+            order, forward + backward through the model class, failed rows and the histogram of evaluations per row
 Prints one JSON object per config."""
 import json
 import os
@@ -332,3 +336,38 @@ if "density" in which:
                           "ms_mix_derivatives": ms_deriv, "ms_bubble_dew_point": ms_point, "ms_forward_backward": ms_fb,
                           "failed": int(r["status"].sum()), "failed_point": int(rp["status"].sum()),
                           "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
+if "gc_density" in which:
+    # one row per lane in class order, no work queue: a wave pays its slowest row.  The neighbours on the same rows: one state
+    # evaluation (pcs_gc_derivatives at the root) and the bubble / dew solve that gave the pressure
+    from feos_torch_amd import GcPcSaftMix
+    n = 1_000_000
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    par = tuple(torch.tensor([v[k] for _, v in table], dtype=torch.float64, requires_grad=True) for k in range(8))
+    phi_leaf = d(b["phi"]).requires_grad_(True)
+    model = GcPcSaftMix(ident, par, b["segment_lists"], b["bond_lists"], b["kab_list"], phi_leaf)
+    tab, S, rows = model._table(), model.S, model.rows
+    phi, T, x, p0 = phi_leaf.detach(), d(b["T"]), d(b["x"]), d(b["p_init"])
+    order = native.gc_class_order(tab, S, rows)
+    for phase, factor in ((0, 3.0), (1, 0.5)):
+        ms_point, rp = timed(lambda: native.gc_bubble_dew(tab, S, rows, phi, T, x, p0, bool(phase), order=order), reps=3)
+        p = torch.where(rp["status"], torch.full_like(rp["p"], 1e5), factor * rp["p"]).contiguous()
+        ms, r = timed(lambda: native.gc_density(tab, S, rows, phi, T, p, x, phase, order=order), reps=5)
+        ms_plain, r_plain = timed(lambda: native.gc_density(tab, S, rows, phi, T, p, x, phase), reps=5)
+        same = all(torch.equal(r[k], r_plain[k]) for k in ("rho", "dpdrho", "status", "iters"))
+        ok = ~r["status"]
+        rho2 = torch.stack((x * r["rho"], (1.0 - x) * r["rho"]), dim=1).contiguous()
+        rho2[r["status"]] = 5e-3
+        ms_deriv, _ = timed(lambda: native.gc_derivatives(tab, S, rows, phi, T, rho2), reps=5)
+
+        def fwd_bwd():
+            model.rows, model.phi, model._order = rows, phi_leaf, order  # the call reduces the model: start from all rows
+            leaves = [v.clone().requires_grad_(True) for v in (T, p, x)]
+            rho, _ = (model.vapor_density if phase else model.liquid_density)(*leaves)
+            rho.sum().backward()
+            return leaves[0].grad
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        print(json.dumps({"config": f"GcPcSaftMix {'vapor' if phase else 'liquid'}_density batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_without_class_order": ms_plain, "same_bits_without_class_order": bool(same), "ms_gc_derivatives": ms_deriv,
+                          "ms_bubble_dew_point": ms_point, "ms_forward_backward": ms_fb, "failed": int(r["status"].sum()),
+                          "failed_point": int(rp["status"].sum()), "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
