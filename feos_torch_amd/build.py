@@ -54,8 +54,10 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # -DPCS_CONST_TABLES (part 1 only): polynomial constants of the fp64 logarithm and of the pressure-only fp64 evaluation are read
 # from constant memory into scalar registers instead of being moved into vector registers as literals (dual.hpp, pure_model.hpp):
 # k_pure_vle<true> 0.7388 -> 0.7329 ms per 1e7 rows (scripts/dev/ab_alternate.py).
+# -DPCS_FAST_SQRT: the association square root of the pressure-only fp64 finish from v_rsq_f64 with a coupled refinement instead
+# of the library's (d_sqrt_fin, dual.hpp); without it that call is the library square root (A/B builds).
 RELAXED = ["-fno-honor-nans", "-fno-honor-infinities", "-fno-signed-zeros", "-fno-slp-vectorize", "-DPCS_FAST_RCP", "-DPCS_FAST_LOG",
-           "-DPCS_F32_PRESOLVE"]
+           "-DPCS_F32_PRESOLVE", "-DPCS_FAST_SQRT"]
 REASSOC = ["-fassociative-math", "-freciprocal-math"]  # part 1 of pure_kernels.hip only
 RELAXED_SOURCES = {"pure_kernels.hip"}
 # mixture / gc solver units: the short logarithm and the refined hardware reciprocal in their guarded forms (=2: IEEE

@@ -103,6 +103,41 @@ PCS_DEV double d_recip(double x) {
 #else
 PCS_DEV double d_recip(double x) { return 1.0 / x; }
 #endif
+// The pressure-only fp64 finish of the pure-component VLE kernel (pure_a<double, D1s>, vle_step<true>) takes shorter forms of
+// the reciprocal and of the association square root.  They are separate names because their results differ from d_recip /
+// d_sqrt in the last bit: the gradient kernels of the same unit, whose outputs are pinned bit for bit, keep those.
+//   d_recip3 (PCS_FAST_RCP == 1): ONE third-order step r (1 + e + e^2), e = 1 - x r, on the hardware estimate: 3 dependent fma
+//     instead of the 4 of two Newton steps, error e^3 = 2^-69 for the loosest seed the ISA text allows (2^-23), below the
+//     final rounding (<= 1 ulp; 0.5 ulp on the host restatement with seeds off by up to 2^-22, tests/tools/fast_math_check.cpp).
+//     0, denormals, inf and NaN make e a NaN and come out as NaN, as with d_recip.
+//   d_sqrt_fin (PCS_FAST_SQRT): the library sqrt() is correctly rounded and scales its argument; the argument here,
+//     aux^2 + 4 rho Delta >= aux^2, is well scaled.  y = v_rsq_f64(x), g = x y ~ sqrt x, h = y / 2 ~ 1 / (2 sqrt x), one coupled
+//     step on (g, h) with r = 1/2 - g h (error of g: 1.5 e^2 for a seed error e), then one residual correction
+//     g += (x - g^2) h (error (1.5 e^2)^2 / 2): <= 2 ulp asked, 0.5 ulp on the host restatement.  Anything but a positive normal
+//     argument gives NaN by a bit test, as in d_log: the solvers recognise failed states by a non-finite result.
+#if defined(PCS_FAST_RCP) && PCS_FAST_RCP == 1
+PCS_DEV double d_recip3(double x) {
+    const double r = __builtin_amdgcn_rcp(x);
+    const double e = __builtin_fma(-x, r, 1.0);
+    return __builtin_fma(r, __builtin_fma(e, e, e), r);
+}
+#else
+PCS_DEV double d_recip3(double x) { return d_recip(x); }
+#endif
+#ifdef PCS_FAST_SQRT
+PCS_DEV double d_sqrt_fin(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    const double r = __builtin_fma(-g, h, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    if (!__builtin_amdgcn_class(x, 0x100)) g = __longlong_as_double(0x7ff8000000000000LL);  // not a +normal number
+    return g;
+}
+#else
+PCS_DEV double d_sqrt_fin(double x) { return d_sqrt(x); }
+#endif
 // NaN / inf test that survives -fno-honor-nans style flags (pure bit test)
 PCS_DEV bool is_finite_bits(double x) {
     return ((unsigned long long)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
@@ -225,6 +260,7 @@ PCS_DEV D1s operator-(double b, const D1s& a) { return D1s(b - a.v, -a.d1); }
 PCS_DEV D1s operator*(const D1s& a, double b) { return D1s(a.v * b, a.d1 * b); }
 PCS_DEV D1s operator*(double b, const D1s& a) { return D1s(a.v * b, a.d1 * b); }
 PCS_DEV D1s d_recip(const D1s& a) { double r = d_recip(a.v); return a.chain(r, -(r * r)); }
+PCS_DEV D1s d_recip3(const D1s& a) { double r = d_recip3(a.v); return a.chain(r, -(r * r)); }
 PCS_DEV D1s d_log(const D1s& a) { return a.chain(d_log(a.v), d_recip(a.v)); }
 PCS_DEV D1s d_sqrt(const D1s& a) { double s = d_sqrt(a.v); return a.chain(s, 0.5 * d_recip(s)); }
 

@@ -286,6 +286,7 @@ PCS_DEV R pure_a(const PureCoef<P>& c, const R& rho) {
 // pre-solve does (pure_f32.hpp): a = rho F(eta) + rho^2 G(eta),
 //   F = m HS - (m-1) ln g,  HS = (4 eta - 3 eta^2) u^2,  HS' = (4 - 2 eta) u^3,  (ln g)' = 3u - w,  u = 1/(1-eta), w = 1/(2-eta)
 //   G = kd1 I1 + kd2 C I2,  C = 1/D,  D = 1 + m A - (m-1) B,  A' = (8 + 20 eta - 4 eta^2) u^5,  B' = q (poly' + 2 poly (u + w)), q = u^2 w^2
+// Reciprocals and the association square root in their short forms (d_recip3, d_sqrt_fin, dual.hpp).
 #ifdef PCS_CONST_TABLES
 // The integer constants of A, A', poly, poly' below from constant memory, as the logarithm's (dual.hpp): 16 fewer v_mov_b32
 // per evaluation.
@@ -296,7 +297,7 @@ constexpr double D1S_K[7] = {8.0, 20.0, -27.0, 12.0, -54.0, 36.0, -8.0};
 template <>
 PCS_DEV D1s pure_a<double, D1s>(const PureCoef<double>& c, const D1s& rho) {
     const double r = rho.v, eta = r * c.ceta;
-    const double u = d_recip(1.0 - eta), w = d_recip(2.0 - eta);
+    const double u = d_recip3(1.0 - eta), w = d_recip3(2.0 - eta);
     const double u2 = u * u, u3 = u2 * u, u4 = u2 * u2;
     const double HS = eta * (4.0 - 3.0 * eta) * u2, HS1 = (4.0 - 2.0 * eta) * u3;
     const double LG = d_log((1.0 - 0.5 * eta) * u3), LG1 = 3.0 * u - w;
@@ -310,7 +311,7 @@ PCS_DEV D1s pure_a<double, D1s>(const PureCoef<double>& c, const D1s& rho) {
     const double q = u2 * (w * w);
     const double B = poly * q, B1 = q * (poly1 + 2.0 * poly * (u + w));
     const double D = 1.0 + c.m * A - c.mm1 * B, D1_ = c.m * A1 - c.mm1 * B1;
-    const double C = d_recip(D), C1 = -D1_ * (C * C);
+    const double C = d_recip3(D), C1 = -D1_ * (C * C);
     const double G = c.kd1 * I1.v + c.kd2 * (C * I2.v);
     const double G1 = c.kd1 * I1.d1 + c.kd2 * (C1 * I2.v + C * I2.d1);
     const double rc = r * c.ceta;
@@ -320,27 +321,27 @@ PCS_DEV D1s pure_a<double, D1s>(const PureCoef<double>& c, const D1s& rho) {
         if (c.polar) {
             D1s J1 = horner_eta<5>(c.j1, eta_d);
             D1s J2 = horner_eta<4>(c.j2, eta_d);
-            a = a + ((rho * rho) * c.qm) * ((J1 * J1) * d_recip(J1 - rho * J2));
+            a = a + ((rho * rho) * c.qm) * ((J1 * J1) * d_recip3(J1 - rho * J2));
         }
         if (c.assoc) {
             // closed form, value and first derivative (see assoc_closed_f32, pure_f32.hpp): a_assoc = rho q(S),
             // a' = q + rho q_S S',  q_S = -na nb XA XB (the energy is stationary in the site fractions), S = rho da h(eta)
-            const double u_ = d_recip(1.0 - eta), eu = eta * u_;
+            const double u_ = d_recip3(1.0 - eta), eu = eta * u_;
             const double h = u_ * (1.0 + eu * (1.5 + 0.5 * eu));
             const double h1 = (u_ * u_) * (2.5 + eu * (4.0 + 1.5 * eu));
             const double S = r * c.da * h, S1 = c.da * (h + eta * h1);
             const double sa = c.na * S, sb = c.nb * S, t = sb - sa, aux = 1.0 - t;
-            const double sq = d_sqrt(aux * aux + 4.0 * sb);
+            const double sq = d_sqrt_fin(aux * aux + 4.0 * sb);
             double xa, xb;
             if (t > 0.5) {
-                xa = 2.0 * d_recip(sq + 1.0 + t);
-                xb = (sq - 1.0 + t) * d_recip(2.0 * sb);
+                xa = 2.0 * d_recip3(sq + 1.0 + t);
+                xb = (sq - 1.0 + t) * d_recip3(2.0 * sb);
             } else if (t < -0.5) {
-                xa = (sq - 1.0 - t) * d_recip(2.0 * sa);
-                xb = 2.0 * d_recip(sq + 1.0 - t);
+                xa = (sq - 1.0 - t) * d_recip3(2.0 * sa);
+                xb = 2.0 * d_recip3(sq + 1.0 - t);
             } else {
-                xa = 2.0 * d_recip(sq + 1.0 + t);
-                xb = 2.0 * d_recip(sq + 1.0 - t);
+                xa = 2.0 * d_recip3(sq + 1.0 + t);
+                xb = 2.0 * d_recip3(sq + 1.0 - t);
             }
             const double q = c.na * (d_log(xa) - 0.5 * xa + 0.5) + c.nb * (d_log(xb) - 0.5 * xb + 0.5);
             const double q1 = -(c.na * c.nb) * (xa * xb);

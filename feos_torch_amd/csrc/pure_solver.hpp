@@ -173,13 +173,14 @@ PCS_DEV bool vapour_is_physical(double p_star, double rho_v) { return gt0(p_star
 struct VleStep {
     double p_star, p_corr, dl, dv;
 };
-// il, iv = 1/l.dp, 1/v.dp
+// il, iv = 1/l.dp, 1/v.dp.  SHORT (the pressure-only fp64 finish): the three reciprocals by d_recip3 (dual.hpp)
+template <bool SHORT = false>
 PCS_DEV VleStep vle_step(const Eval& l, const Eval& v, double rl, double rv, double il, double iv) {
     VleStep s;
     // d_recip / d_log: the refined hardware reciprocal and the short logarithm where the unit is built with
     // PCS_FAST_RCP / PCS_FAST_LOG (dual.hpp), the IEEE division and library log otherwise
-    double inv_v = d_recip(rv), inv_l = d_recip(rl);
-    double inv_dv = d_recip(inv_v - inv_l);
+    double inv_v = SHORT ? d_recip3(rv) : d_recip(rv), inv_l = SHORT ? d_recip3(rl) : d_recip(rl);
+    double inv_dv = SHORT ? d_recip3(inv_v - inv_l) : d_recip(inv_v - inv_l);
     s.p_star = -(v.a * inv_v - l.a * inv_l + d_log(rv * inv_l)) * inv_dv;
     double rl_res = l.p - s.p_star, rv_res = v.p - s.p_star;
     s.dl = -rl_res * il;
@@ -332,7 +333,7 @@ PCS_DEV int vle_lite_finish(const double* par, double T, bool warm, double rl, d
             D1s av = pure_a<double, D1s>(c, D1s(rv, 1.0));
             le.a = al.v; le.p = rl - al.v + rl * al.d1;
             ve.a = av.v; ve.p = rv - av.v + rv * av.d1;
-            VleStep s = vle_step(le, ve, rl, rv, il, iv);
+            VleStep s = vle_step<true>(le, ve, rl, rv, il, iv);
             bool ok = is_finite_bits(s.p_star) && is_finite_bits(s.dl) && is_finite_bits(s.dv);
             double rl_new = rl + s.dl, rv_new = rv + s.dv;
             ok = ok && (rl_new > 0.0) && (rv_new > 0.0) && (rv_new < rl_new);
