@@ -34,6 +34,7 @@
 
 namespace {
 
+// persistent grid: at most GS_GRID * GSBLOCK / BLOCK workgroups (GSBLOCK = one wave; 682 of 192 threads, 512 of 256); two tests read both
 constexpr int GSBLOCK = 64;
 constexpr int GS_GRID = 2048;
 // MODE 2 is MODE 0 for TWO functionals of the converged point at once, the pressure and the incipient-phase mole fraction y0
@@ -46,31 +47,28 @@ template <int MODE> struct GsChunk { static constexpr int value = MODE != 1 ? 2 
 // bond diameters, which double as the lane-strided coefficient-adjoint array of MODE 0 (ADJ_SLOTS); the row bytes follow (stage_row)
 // (MODE 0: the coefficient adjoints, the dual model is not instantiated; MODE 1: the dual model with CH = 1 direction)
 template <int MODE> struct GsPerThread { static constexpr int value = 2 * GC_MAXE + (MODE != 1 ? ADJ_SLOTS : 2 * GC_MAXE * (1 + GsChunk<1>::value)); };
+// LDS of a workgroup: table + gradient accumulator + per thread GsPerThread doubles and the row bytes
+constexpr size_t gs_lds_bytes(int S, int block, int mode) {
+    return gc_lds_bytes(S, block, (mode != 1 ? GsPerThread<0>::value : GsPerThread<1>::value) + GC_ROW_LDS_DOUBLES) + sizeof(double) * S * 8;
+}
+// Workgroup size per mode.  The kernel holds a full register file per wave and waits mostly for its own stack frame, so the
+// number of resident waves is what counts (measured: one wave per CU 6.6 ms, two 3.8 ms per 1e6 rows): a workgroup of several
+// waves shares ONE copy of the table, and the block is the largest whose request stays within the CU's 160 KB at the largest
+// table the ABI admits:
+//   MODE 0 and MODE 2 (bubble / dew, 88 doubles per thread): 24 S^2 + 128 S + 704 BLOCK bytes.  256 threads need 180 224 B before
+//     the table and never fit; 192 threads fit for every S (S = 22: 149 KB; S = 32: 163 840 B, exactly the CU's LDS);
+//   MODE 1 (VJP of `derivatives`, 59 doubles per thread): 256 threads fit for every S (S = 32: 149 504 B).
+// (tests/test_gc_point_grad_gpu.py, tests/test_gc_state_gpu.py)
+template <int MODE> struct GsBlock { static constexpr int value = MODE != 1 ? 192 : 256; };
+constexpr size_t GS_LDS_CU = 160 * 1024;
+static_assert(gs_lds_bytes(GC_MAXS, GsBlock<0>::value, 0) <= GS_LDS_CU && gs_lds_bytes(GC_MAXS, GsBlock<2>::value, 2) <= GS_LDS_CU,
+              "gc_gradient.hip, GsBlock<0 / 2>: the workgroup's LDS at GC_MAXS exceeds the CU's 160 KB");
+static_assert(gs_lds_bytes(GC_MAXS, GsBlock<1>::value, 1) <= GS_LDS_CU, "gc_gradient.hip, GsBlock<1>: the workgroup's LDS at GC_MAXS exceeds the CU's 160 KB");
 
 enum : int { Q_M, Q_Z1, Q_Z2, Q_Z3, Q_S3, Q_EK, Q_MU, Q_SA, Q_EA, Q_KA, Q_EAB, Q_NA, Q_NB, Q_COUNT };
 
-// Accumulation into the workgroup's [S,8] gradient table in LDS: ds_add_f64 per contributing lane (0 = 0).
-// 0 = 1 (experiment, off): the workgroup is ONE wave and with class-ordered rows many of its lanes add to the
-// same table entry at the same time; there the lanes that target the same entry are summed with a DPP butterfly and ONE
-// lane does a plain read-modify-write, once per distinct entry in the wave.  Measured on 1e6 rows: 6.55 ms against 4.71 ms
-// with the atomics -- the waits of this kernel (PMC: 71 % of the wave cycles) are not the LDS atomics.  Either way every
-// lane of the wave reaches the call (on = this lane contributes).
-__device__ __forceinline__ double wave_sum(double x) {
-#define PCS_DPP_STEP(ctrl, rmask)                                                                \
-    {                                                                                            \
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), ctrl, rmask, 0xf, false); \
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), ctrl, rmask, 0xf, false); \
-        x += __hiloint2double(hi, lo);                                                           \
-    }
-    PCS_DPP_STEP(0xB1, 0xf)   // quad_perm [1,0,3,2]
-    PCS_DPP_STEP(0x4E, 0xf)   // quad_perm [2,3,0,1]
-    PCS_DPP_STEP(0x141, 0xf)  // row_half_mirror
-    PCS_DPP_STEP(0x140, 0xf)  // row_mirror: every lane holds its row's sum
-    PCS_DPP_STEP(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
-    PCS_DPP_STEP(0x143, 0xc)  // row_bcast:31 into rows 2 and 3: lane 63 holds the total
-#undef PCS_DPP_STEP
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
-}
+// Accumulation into the workgroup's [S,8] gradient table in LDS: ds_add_f64 per contributing lane; every lane of the wave
+// reaches the call (on = this lane contributes).  Summing the lanes of a wave first was tried and is slower.
 __device__ __forceinline__ void lds_add(double* p, double v, bool on) {
     if (on) unsafeAtomicAdd(p, v);
 }
@@ -284,7 +282,161 @@ struct GcGradArgs {
     const double* gout_y;  // MODE 2: upstream dL/dy0 [n] or NULL (= 0)
 };
 
-// BLOCK: 64, or 192 where the LDS of three waves fits one CU next to ONE copy of the table (launch_gc_gradient)
+// density points of a row's functional: MODE 0 / 2 (s0, s1) = specified and (i0, i1) = incipient phase; MODE 1 both the state point
+struct RowPoints { double s0, s1, i0, i1; };
+// the row's weights: MODE 0 / 2 the phase constants (alpha, beta) of the two points ([0] specified, [1] incipient) and whether the
+// adjoint solve succeeded; MODE 1 the weights dw of the six Taylor coefficients
+struct PointWeights { double alpha[2], beta0[2], beta1[2]; DerivWeights dw; bool ok; };
+
+// the two probe flavours: seeds of the density arguments (`zero` carries the scalar type) and the contraction of a result with
+// the row's weights
+template <int MODE>
+struct Probe {
+    const PointWeights& w;
+    const RowPoints& r;
+    template <class X> __device__ __forceinline__ typename ProbeT<MODE, X>::type seed0(int pt, X zero) const {
+        if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? r.s0 : r.i0), X(pt == 0 ? w.beta0[0] : w.beta0[1]));
+        else return T2<X>(X(r.s0), X(1.0), X(0.0), X(0.0), X(0.0), X(0.0));
+    }
+    template <class X> __device__ __forceinline__ typename ProbeT<MODE, X>::type seed1(int pt, X zero) const {
+        if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? r.s1 : r.i1), X(pt == 0 ? w.beta1[0] : w.beta1[1]));
+        else return T2<X>(X(r.s1), X(0.0), X(1.0), X(0.0), X(0.0), X(0.0));
+    }
+    template <class G> __device__ __forceinline__ double dot_g(const typename ProbeT<MODE, G>::type& a, int pt, int j) const {
+        if constexpr (MODE != 1) return (pt == 0 ? w.alpha[0] : w.alpha[1]) * a.v.e[j] + a.d1.e[j];
+        else return deriv_contract(w.dw, a, j);
+    }
+    __device__ __forceinline__ double dot_q(const typename ProbeT<MODE, double>::type& a, int pt) const {
+        if constexpr (MODE != 1) return (pt == 0 ? w.alpha[0] : w.alpha[1]) * a.v + a.d1;
+        else return w.dw.cv * a.v + w.dw.cg0 * a.g0 + w.dw.cg1 * a.g1 + w.dw.ch00 * a.h00 + w.dw.ch01 * a.h01 + w.dw.ch11 * a.h11;
+    }
+};
+
+// chain from a molecule-level sum (quantity q of molecule j, gq = weight x d functional / d sum) to the segment parameters of
+// that molecule's entries: row = the row bytes, tb = the staged table, acc = the workgroup's gradient table
+__device__ __forceinline__ void chain(const unsigned char* row, const GcTable& tb, double* acc, double rT, int q, int j, double gq, bool on_q) {
+#pragma unroll 1
+    for (int e = 0; e < GC_MAXE; e++) {
+        const int cnt = row[16 + j * GC_MAXE + e];
+        const bool on = on_q && cnt != 0;
+        if (__ballot(on) == 0ull) continue;
+        const int a = row[j * GC_MAXE + e];
+        const double* p = tb.seg + 8 * a;
+        double* ga = acc + 8 * a;
+        const double gn = gq * cnt;
+        if (q == Q_M) {
+            lds_add(ga + 0, gn, on);
+        } else if (q <= Q_Z3) {
+            double d, ds, de;
+            diameter_grad(p, rT, d, ds, de);
+            const int k = q - Q_Z1 + 1;                                   // Z_k = sum n m d^k
+            const double dk1 = (k == 1) ? 1.0 : (k == 2 ? d : d * d);     // d^(k-1)
+            lds_add(ga + 0, gn * dk1 * d, on);
+            const double t = gn * p[0] * (k * dk1);
+            lds_add(ga + 1, t * ds, on);
+            lds_add(ga + 2, t * de, on);
+        } else if (q == Q_S3) {
+            lds_add(ga + 0, gn * p[1] * p[1] * p[1], on);
+            lds_add(ga + 1, gn * p[0] * 3.0 * p[1] * p[1], on);
+        } else if (q == Q_EK) {
+            lds_add(ga + 0, gn * p[2], on);
+            lds_add(ga + 2, gn * p[0], on);
+        } else if (q == Q_MU) {
+            lds_add(ga + 3, gn * 2.0 * p[3], on);
+        } else if (q == Q_SA) {
+            lds_add(ga + 1, gn * sgn_d(p[4] * p[5]), on);
+        } else if (q == Q_EA) {
+            lds_add(ga + 2, gn * sgn_d(p[4] * p[5]), on);
+        } else {
+            lds_add(ga + (q - Q_KA + 4), gn, on);  // kappa_ab, epsilon_k_ab, na, nb: plain sums
+        }
+    }
+}
+
+// ---- (2) dispersion double sums: A[pr] = rT (phi-factor) s1[pr], B[pr] = rT^2 (phi-factor)^2 s2[pr]  (gc_finish)
+__device__ __forceinline__ void dispersion_sums(const double* gA, const double* gB, double ph0, double ph1, const unsigned char* row,
+                                                const GcTable& tb, double* acc, double rT, double wrow, bool live) {
+    const double p01 = sqrt(ph0 * ph1);
+    const double cA[3] = {rT * ph0, rT * 2.0 * p01, rT * ph1};
+    const double cB[3] = {rT * rT * ph0 * ph0, rT * rT * 2.0 * ph0 * ph1, rT * rT * ph1 * ph1};
+#pragma unroll
+    for (int pq = 0; pq < 3; pq++) {
+        const int mi = (pq == 2) ? 1 : 0, mj = (pq == 0) ? 0 : 1;
+        const double gs1 = wrow * gA[pq] * cA[pq], gs2 = wrow * gB[pq] * cB[pq];
+        // two sweeps so that each table entry of the row receives ONE accumulated term per parameter (the sums over
+        // the partner entries stay in registers): side 0 = entries of molecule mi (partner mj), side 1 the reverse
+#pragma unroll 1
+        for (int side = 0; side < 2; side++) {
+            const int mo = side == 0 ? mi : mj, mp = side == 0 ? mj : mi;  // own / partner molecule
+#pragma unroll 1
+            for (int e = 0; e < GC_MAXE; e++) {
+                const int ne = row[16 + mo * GC_MAXE + e];
+                const bool on = live && ne != 0;
+                if (__ballot(on) == 0ull) continue;
+                const int a = row[mo * GC_MAXE + e];
+                const double* pa = tb.seg + 8 * a;
+                double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+#pragma unroll 1
+                for (int f = 0; f < GC_MAXE; f++) {
+                    const int nf = row[16 + mp * GC_MAXE + f];
+                    if (nf == 0) continue;
+                    const int b = row[mp * GC_MAXE + f];
+                    const double* pb = tb.seg + 8 * b;
+                    const double mb = nf * pb[0];
+                    double k1 = 1.0;
+                    if (mi != mj) k1 = tb.K[a * tb.S + b];  // E1, E2, K are symmetric tables
+                    const double t1 = tb.E1[a * tb.S + b] * k1, t2 = tb.E2[a * tb.S + b] * (k1 * k1);
+                    const double common = gs1 * t1 + gs2 * t2;
+                    g0 += mb * common;
+                    const double sab = 0.5 * (pa[1] + pb[1]);
+                    g1 += mb * common * (1.5 / sab);  // d sigma_ab^3 / d sigma_a = 1.5 sigma_ab^2
+                    // E1 = sqrt(eps_a eps_b) sigma_ab^3: d/d eps_a = E1 / (2 eps_a); the square root is not
+                    // differentiable at eps_a = 0 (segment '>C<'): that term is left out (the reference's autograd
+                    // returns NaN for every epsilon_k there).  E2 = eps_a eps_b sigma_ab^3.
+                    const double s3k2 = sab * sab * sab * (k1 * k1);
+                    g2 += mb * ((pa[2] != 0.0 ? gs1 * t1 * (0.5 / pa[2]) : 0.0) + gs2 * pb[2] * s3k2);
+                }
+                const double ma = ne * pa[0];
+                lds_add(acc + 8 * a + 0, ne * g0, on);
+                lds_add(acc + 8 * a + 1, ma * g1, on);
+                lds_add(acc + 8 * a + 2, ma * g2, on);
+            }
+        }
+    }
+}
+
+// ---- MODE 1 only: the per-row directions T (through the full coefficient set-up), rho_0, rho_1 -> g9[6..8]
+template <int BLOCK>
+__device__ __forceinline__ void row_directions(const GcModelT<double>& m, const DerivWeights& dw, double r0, double r1,
+                                               DN<double, GsChunk<1>::value>* gbonds, double T, double ph0, double ph1,
+                                               const unsigned char* row, const GcTable& tb, double* g9, bool live) {
+    typedef DN<double, GsChunk<1>::value> G;
+    typedef T2<G> R;
+    GcCoef<G> c;
+    c.bond_dab = gbonds;
+    c.bond_cnt = m.c.bond_cnt;  // counts are rewritten identically
+    c.stride = BLOCK;
+#pragma unroll 1
+    for (int pass = 0; pass < 3; pass++) {
+        if (pass < 2) {
+            G gT(T);
+            if (pass == 0) gT.e[0] = 1.0;
+            gc_coef<G>(c, row, tb, ph0, ph1, gT);
+        }
+        G q0(r0), q1(r1);
+        if (pass == 1) q0.e[0] = 1.0;
+        if (pass == 2) q1.e[0] = 1.0;
+        const G one(1.0), nul(0.0);
+        R a = gc_a_tangent<G, R>(c, R(q0, one, nul, nul, nul, nul), R(q1, nul, one, nul, nul, nul));
+        const double v = deriv_contract(dw, a, 0);
+        if (!live) continue;
+        if (pass == 0) g9[6] = v;
+        else if (pass == 1) g9[7] = v + dw.x0;
+        else g9[8] = v + dw.x1;
+    }
+}
+
+// BLOCK: GsBlock<MODE>::value, the only instantiation per mode
 template <int MODE, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs A_) {
     const int dew = A_.dew, S = A_.S;
@@ -330,13 +482,12 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
         const unsigned char* row = stage_row(rows + (size_t)i * GC_ROW_BYTES, row_area);  // read byte by byte in the loops below
         const double T = temp[i], ph0 = phi[2 * i], ph1 = phi[2 * i + 1];
         const double rT = 1.0 / T;
-        // density points of the functional: pt 0 = specified phase (MODE 0) or the state point (MODE 1), pt 1 = incipient phase
-        double s0, s1, i0, i1;
+        RowPoints r;
         if (MODE != 1) {
             const double4 r4 = reinterpret_cast<const double4*>(A_.rho)[i];  // (V0, V1, L0, L1)
-            s0 = dew ? r4.x : r4.z; s1 = dew ? r4.y : r4.w; i0 = dew ? r4.z : r4.x; i1 = dew ? r4.w : r4.y;
+            r.s0 = dew ? r4.x : r4.z; r.s1 = dew ? r4.y : r4.w; r.i0 = dew ? r4.z : r4.x; r.i1 = dew ? r4.w : r4.y;
         } else {
-            s0 = i0 = A_.rho[2 * i]; s1 = i1 = A_.rho[2 * i + 1];
+            r.s0 = r.i0 = A_.rho[2 * i]; r.s1 = r.i1 = A_.rho[2 * i + 1];
         }
 
         GcMol<double, double> ml;
@@ -344,9 +495,10 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
         gc_mol<double>(ml, m.c.bond_dab, m.c.stride, row, tb, rT);
         gc_finish<double, double>(m.c, ml, ph0, ph1, rT);
 
-        double alpha[2], beta0[2], beta1[2];
-        DerivWeights dw;
-        bool ok = true;
+        // row weights: MODE 0 / 2 the phase constants from the adjoint solve, MODE 1 the weights of the Taylor coefficients
+        PointWeights pw;
+        const double s0 = r.s0, s1 = r.s1, i0 = r.i0, i1 = r.i1;
+        pw.ok = true;
         if constexpr (MODE != 1) {
             // adjoint of the converged state (mix_jacobian.hpp): J^T w = dp^vap/du; MODE 2: and J^T wy = dy0/du from the same
             // elimination (mix_incipient.hpp)
@@ -366,10 +518,10 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             J[2][2] = -i1 * nn.dp1();
             double A[3][MODE == 2 ? 5 : 4];
 #pragma unroll
-            for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) {
 #pragma unroll
-                for (int cc = 0; cc < 3; cc++) A[r][cc] = J[cc][r];
-                A[r][3] = 0.0;
+                for (int cc = 0; cc < 3; cc++) A[k][cc] = J[cc][k];
+                A[k][3] = 0.0;
             }
             if (dew) {
                 A[0][3] = J[2][0];
@@ -379,102 +531,44 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             }
             double w[3];
             if constexpr (MODE == 0) {
-                ok = solve3(A, w);
+                pw.ok = solve3(A, w);
                 if (dew) {  // the specified phase is the vapour
                     const double u = 1.0 - w[2];
-                    alpha[0] = -u;     beta0[0] = u * s0 - w[0];     beta1[0] = u * s1 - w[1];
-                    alpha[1] = -w[2];  beta0[1] = w[2] * i0 + w[0];  beta1[1] = w[2] * i1 + w[1];
+                    pw.alpha[0] = -u;     pw.beta0[0] = u * s0 - w[0];     pw.beta1[0] = u * s1 - w[1];
+                    pw.alpha[1] = -w[2];  pw.beta0[1] = w[2] * i0 + w[0];  pw.beta1[1] = w[2] * i1 + w[1];
                 } else {
                     const double u = 1.0 + w[2];
-                    alpha[0] = w[2];   beta0[0] = -w[2] * s0 - w[0]; beta1[0] = -w[2] * s1 - w[1];
-                    alpha[1] = -u;     beta0[1] = u * i0 + w[0];     beta1[1] = u * i1 + w[1];
+                    pw.alpha[0] = w[2];   pw.beta0[0] = -w[2] * s0 - w[0]; pw.beta1[0] = -w[2] * s1 - w[1];
+                    pw.alpha[1] = -u;     pw.beta0[1] = u * i0 + w[0];     pw.beta1[1] = u * i1 + w[1];
                 }
             } else {
                 A[0][4] = 0.0;
                 A[1][4] = y0 * y1;
                 A[2][4] = -(y0 * y1);
                 double wy[3];
-                ok = solve3_pair(A, w, wy);
-                // (alpha, beta) = g_p T P_UNIT (alpha, beta)_p + g_y (alpha, beta)_y; the row weight below is 1
+                pw.ok = solve3_pair(A, w, wy);
+                // (alpha, beta) = g_p T P_UNIT (alpha, beta)_p + g_y (alpha, beta)_y; the row weight is 1
                 const double cp = (gout ? gout[i] : 0.0) * (T * P_UNIT), cy = A_.gout_y ? A_.gout_y[i] : 0.0;
                 const double us = dew ? -(1.0 - w[2]) : w[2];   // alpha_p of the specified phase
                 const double ui = dew ? -w[2] : -(1.0 + w[2]);  // alpha_p of the incipient phase
-                alpha[0] = cp * us + cy * wy[2];
-                beta0[0] = cp * (-us * s0 - w[0]) + cy * (-wy[2] * s0 - wy[0]);
-                beta1[0] = cp * (-us * s1 - w[1]) + cy * (-wy[2] * s1 - wy[1]);
-                alpha[1] = cp * ui - cy * wy[2];
-                beta0[1] = cp * (-ui * i0 + w[0]) + cy * (wy[2] * i0 + wy[0]);
-                beta1[1] = cp * (-ui * i1 + w[1]) + cy * (wy[2] * i1 + wy[1]);
+                pw.alpha[0] = cp * us + cy * wy[2];
+                pw.beta0[0] = cp * (-us * s0 - w[0]) + cy * (-wy[2] * s0 - wy[0]);
+                pw.beta1[0] = cp * (-us * s1 - w[1]) + cy * (-wy[2] * s1 - wy[1]);
+                pw.alpha[1] = cp * ui - cy * wy[2];
+                pw.beta0[1] = cp * (-ui * i0 + w[0]) + cy * (wy[2] * i0 + wy[0]);
+                pw.beta1[1] = cp * (-ui * i1 + w[1]) + cy * (wy[2] * i1 + wy[1]);
             }
         } else {
             const PhaseEval e = phase_eval(m, s0, s1);
-            dw = deriv_weights(e, A_.g_a ? A_.g_a[i] : 0.0, A_.g_p ? A_.g_p[i] : 0.0, A_.g_mu ? A_.g_mu[2 * i] : 0.0,
-                               A_.g_mu ? A_.g_mu[2 * i + 1] : 0.0, A_.g_v ? A_.g_v[2 * i] : 0.0, A_.g_v ? A_.g_v[2 * i + 1] : 0.0);
-            alpha[0] = alpha[1] = beta0[0] = beta0[1] = beta1[0] = beta1[1] = 0.0;
+            pw.dw = deriv_weights(e, A_.g_a ? A_.g_a[i] : 0.0, A_.g_p ? A_.g_p[i] : 0.0, A_.g_mu ? A_.g_mu[2 * i] : 0.0,
+                                  A_.g_mu ? A_.g_mu[2 * i + 1] : 0.0, A_.g_v ? A_.g_v[2 * i] : 0.0, A_.g_v ? A_.g_v[2 * i + 1] : 0.0);
+            pw.alpha[0] = pw.alpha[1] = pw.beta0[0] = pw.beta0[1] = pw.beta1[0] = pw.beta1[1] = 0.0;
         }
-        // the two probe flavours: seeds of the density arguments and the contraction of a result with the row's weights
-        auto seed0 = [&](int pt, auto zero) {
-            typedef decltype(zero) X;
-            if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? s0 : i0), X(pt == 0 ? beta0[0] : beta0[1]));
-            else return T2<X>(X(s0), X(1.0), X(0.0), X(0.0), X(0.0), X(0.0));
-        };
-        auto seed1 = [&](int pt, auto zero) {
-            typedef decltype(zero) X;
-            if constexpr (MODE != 1) return D1<X>(X(pt == 0 ? s1 : i1), X(pt == 0 ? beta1[0] : beta1[1]));
-            else return T2<X>(X(s1), X(0.0), X(1.0), X(0.0), X(0.0), X(0.0));
-        };
-        auto dot_g = [&](const R& a, int pt, int j) -> double {
-            if constexpr (MODE != 1) return (pt == 0 ? alpha[0] : alpha[1]) * a.v.e[j] + a.d1.e[j];
-            else return deriv_contract(dw, a, j);
-        };
-        auto dot_q = [&](const Q1& a, int pt) -> double {
-            if constexpr (MODE != 1) return (pt == 0 ? alpha[0] : alpha[1]) * a.v + a.d1;
-            else return dw.cv * a.v + dw.cg0 * a.g0 + dw.cg1 * a.g1 + dw.ch00 * a.h00 + dw.ch01 * a.h01 + dw.ch11 * a.h11;
-        };
+        const Probe<MODE> probe{pw, r};
         // weight of this row: upstream gradient x (reduced -> Pa); a singular adjoint poisons the result like the
         // per-row NaN of k_gc_point_jacobian (MODE 2: the upstream gradients are inside alpha and beta)
-        const double wrow = !live ? 0.0 : MODE == 0 ? (ok ? (gout ? gout[i] : 1.0) * (T * P_UNIT) : nanv) : MODE == 2 ? (ok ? 1.0 : nanv) : 1.0;
+        const double wrow = !live ? 0.0 : MODE == 0 ? (pw.ok ? (gout ? gout[i] : 1.0) * (T * P_UNIT) : nanv) : MODE == 2 ? (pw.ok ? 1.0 : nanv) : 1.0;
 
-        // chain from a molecule-level sum (quantity q of molecule j, gq = weight x d functional / d sum) to the segment
-        // parameters of that molecule's entries
-        auto chain = [&](int q, int j, double gq, bool on_q) {
-#pragma unroll 1
-            for (int e = 0; e < GC_MAXE; e++) {
-                const int cnt = row[16 + j * GC_MAXE + e];
-                const bool on = on_q && cnt != 0;
-                if (__ballot(on) == 0ull) continue;
-                const int a = row[j * GC_MAXE + e];
-                const double* p = tb.seg + 8 * a;
-                double* ga = acc + 8 * a;
-                const double gn = gq * cnt;
-                if (q == Q_M) {
-                    lds_add(ga + 0, gn, on);
-                } else if (q <= Q_Z3) {
-                    double d, ds, de;
-                    diameter_grad(p, rT, d, ds, de);
-                    const int k = q - Q_Z1 + 1;                                   // Z_k = sum n m d^k
-                    const double dk1 = (k == 1) ? 1.0 : (k == 2 ? d : d * d);     // d^(k-1)
-                    lds_add(ga + 0, gn * dk1 * d, on);
-                    const double t = gn * p[0] * (k * dk1);
-                    lds_add(ga + 1, t * ds, on);
-                    lds_add(ga + 2, t * de, on);
-                } else if (q == Q_S3) {
-                    lds_add(ga + 0, gn * p[1] * p[1] * p[1], on);
-                    lds_add(ga + 1, gn * p[0] * 3.0 * p[1] * p[1], on);
-                } else if (q == Q_EK) {
-                    lds_add(ga + 0, gn * p[2], on);
-                    lds_add(ga + 2, gn * p[0], on);
-                } else if (q == Q_MU) {
-                    lds_add(ga + 3, gn * 2.0 * p[3], on);
-                } else if (q == Q_SA) {
-                    lds_add(ga + 1, gn * sgn_d(p[4] * p[5]), on);
-                } else if (q == Q_EA) {
-                    lds_add(ga + 2, gn * sgn_d(p[4] * p[5]), on);
-                } else {
-                    lds_add(ga + (q - Q_KA + 4), gn, on);  // kappa_ab, epsilon_k_ab, na, nb: plain sums
-                }
-            }
-        };
         // ---- (1) molecule-level sums -------------------------------------------------------------------------------
         if constexpr (MODE != 1) {
             // coefficient adjoints of both phases (closed form), then their chain to the 26 sums
@@ -483,8 +577,8 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             for (int k = 0; k < ADJ_SLOTS; k++) adj[k * BLOCK] = 0.0;
 #pragma unroll 1
             for (int pt = 0; pt < 2; pt++)
-                gc_a_adjoint(m.c, pt == 0 ? s0 : i0, pt == 0 ? s1 : i1, pt == 0 ? beta0[0] : beta0[1], pt == 0 ? beta1[0] : beta1[1],
-                             pt == 0 ? alpha[0] : alpha[1], adj, BLOCK);
+                gc_a_adjoint(m.c, pt == 0 ? r.s0 : r.i0, pt == 0 ? r.s1 : r.i1, pt == 0 ? pw.beta0[0] : pw.beta0[1], pt == 0 ? pw.beta1[0] : pw.beta1[1],
+                             pt == 0 ? pw.alpha[0] : pw.alpha[1], adj, BLOCK);
             double val[Q_COUNT * 2];
             gc_finish_gradient(ml, m.c.acls, m.c.polar, rT, adj, BLOCK, val);
             const bool polar = m.c.polar, assoc = m.c.acls != ASSOC_NONE;
@@ -492,8 +586,8 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
             for (int q = 0; q < Q_COUNT; q++) {
                 const bool need = live && ((q <= Q_Z3) || (q <= Q_MU ? polar : assoc));
                 if (__ballot(need) == 0ull) continue;
-                chain(q, 0, wrow * val[2 * q], need);
-                chain(q, 1, wrow * val[2 * q + 1], need);
+                chain(row, tb, acc, rT, q, 0, wrow * val[2 * q], need);
+                chain(row, tb, acc, rT, q, 1, wrow * val[2 * q + 1], need);
             }
         } else {
             // zero-tangent dual copy of the bond diameters (their derivative is part (3))
@@ -513,12 +607,12 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
                 double val[2] = {0.0, 0.0};
 #pragma unroll 1
                 for (int pt = 0; pt < NPT; pt++) {
-                    R a = gc_a_tangent<G, R>(c, seed0(pt, G(0.0)), seed1(pt, G(0.0)));
+                    R a = gc_a_tangent<G, R>(c, probe.seed0(pt, G(0.0)), probe.seed1(pt, G(0.0)));
                     if (CH == 2) {
 #pragma unroll
-                        for (int j = 0; j < 2; j++) val[j] += dot_g(a, pt, j < CH ? j : 0);
+                        for (int j = 0; j < 2; j++) val[j] += probe.template dot_g<G>(a, pt, j < CH ? j : 0);
                     } else {
-                        const double v = dot_g(a, pt, 0);
+                        const double v = probe.template dot_g<G>(a, pt, 0);
                         if (jm == 0) val[0] += v; else val[1] += v;
                     }
                 }
@@ -526,51 +620,27 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     if (CH == 1 && j != jm) continue;
-                    chain(q, j, wrow * val[j], need && live);
+                    chain(row, tb, acc, rT, q, j, wrow * val[j], need && live);
                 }
             }
         }
 
-        // ---- MODE 1 only: the per-row directions T, rho_0, rho_1 (T through the full coefficient set-up) -------------
-        if constexpr (MODE == 1) {
-            double* g9 = A_.jac9 + 9 * i;
-            GcCoef<G> c;
-            c.bond_dab = gbonds + threadIdx.x;
-            c.bond_cnt = m.c.bond_cnt;  // counts are rewritten identically
-            c.stride = BLOCK;
-#pragma unroll 1
-            for (int pass = 0; pass < 3; pass++) {  // T (through the full coefficient set-up), rho_0, rho_1
-                if (pass < 2) {
-                    G gT(T);
-                    if (pass == 0) gT.e[0] = 1.0;
-                    gc_coef<G>(c, row, tb, ph0, ph1, gT);
-                }
-                G q0(s0), q1(s1);
-                if (pass == 1) q0.e[0] = 1.0;
-                if (pass == 2) q1.e[0] = 1.0;
-                const G one(1.0), nul(0.0);
-                R a = gc_a_tangent<G, R>(c, R(q0, one, nul, nul, nul, nul), R(q1, nul, one, nul, nul, nul));
-                const double v = deriv_contract(dw, a, 0);
-                if (!live) continue;
-                if (pass == 0) g9[6] = v;
-                else if (pass == 1) g9[7] = v + dw.x0;
-                else g9[8] = v + dw.x1;
-            }
-        }
+        if constexpr (MODE == 1)
+            row_directions<BLOCK>(m, pw.dw, r.s0, r.s1, gbonds + threadIdx.x, T, ph0, ph1, row, tb, A_.jac9 + 9 * i, live);
 
         // ---- (2) dispersion double sums and (3) bond diameters: closed forms in the probe type over double ----------
         double gA[3] = {0.0, 0.0, 0.0}, gB[3] = {0.0, 0.0, 0.0};
         Q1 pcc[NPT], pz3m1[NPT], pomz[NPT], pr[NPT][2];
 #pragma unroll
         for (int pt = 0; pt < NPT; pt++) {
-            const Q1 r0 = seed0(pt, 0.0), r1 = seed1(pt, 0.0);
+            const Q1 r0 = probe.seed0(pt, 0.0), r1 = probe.seed1(pt, 0.0);
             Q1 F1, F2;
             dispersion_factors(m.c, r0, r1, F1, F2);
             const Q1 q[3] = {r0 * r0, r0 * r1, r1 * r1};
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                gA[k] += dot_q(F1 * q[k], pt);
-                gB[k] += dot_q(F2 * q[k], pt);
+                gA[k] += probe.dot_q(F1 * q[k], pt);
+                gB[k] += probe.dot_q(F2 * q[k], pt);
             }
             const Q1 zeta2 = r0 * m.c.zk[2][0] + r1 * m.c.zk[2][1];
             const Q1 zeta3 = r0 * m.c.zk[3][0] + r1 * m.c.zk[3][1];
@@ -589,56 +659,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
                 for (int k = 0; k < 3; k++) { A_.agg[6 * i + k] = m.c.A[k]; A_.agg[6 * i + 3 + k] = m.c.B[k]; }
             }
         }
-        {
-            // A[pr] = rT (phi-factor) s1[pr], B[pr] = rT^2 (phi-factor)^2 s2[pr]  (gc_finish)
-            const double p01 = sqrt(ph0 * ph1);
-            const double cA[3] = {rT * ph0, rT * 2.0 * p01, rT * ph1};
-            const double cB[3] = {rT * rT * ph0 * ph0, rT * rT * 2.0 * ph0 * ph1, rT * rT * ph1 * ph1};
-#pragma unroll
-            for (int pq = 0; pq < 3; pq++) {
-                const int mi = (pq == 2) ? 1 : 0, mj = (pq == 0) ? 0 : 1;
-                const double gs1 = wrow * gA[pq] * cA[pq], gs2 = wrow * gB[pq] * cB[pq];
-                // two sweeps so that each table entry of the row receives ONE accumulated term per parameter (the sums over
-                // the partner entries stay in registers): side 0 = entries of molecule mi (partner mj), side 1 the reverse
-#pragma unroll 1
-                for (int side = 0; side < 2; side++) {
-                    const int mo = side == 0 ? mi : mj, mp = side == 0 ? mj : mi;  // own / partner molecule
-#pragma unroll 1
-                    for (int e = 0; e < GC_MAXE; e++) {
-                        const int ne = row[16 + mo * GC_MAXE + e];
-                        const bool on = live && ne != 0;
-                        if (__ballot(on) == 0ull) continue;
-                        const int a = row[mo * GC_MAXE + e];
-                        const double* pa = tb.seg + 8 * a;
-                        double g0 = 0.0, g1 = 0.0, g2 = 0.0;
-#pragma unroll 1
-                        for (int f = 0; f < GC_MAXE; f++) {
-                            const int nf = row[16 + mp * GC_MAXE + f];
-                            if (nf == 0) continue;
-                            const int b = row[mp * GC_MAXE + f];
-                            const double* pb = tb.seg + 8 * b;
-                            const double mb = nf * pb[0];
-                            double k1 = 1.0;
-                            if (mi != mj) k1 = tb.K[a * tb.S + b];  // E1, E2, K are symmetric tables
-                            const double t1 = tb.E1[a * tb.S + b] * k1, t2 = tb.E2[a * tb.S + b] * (k1 * k1);
-                            const double common = gs1 * t1 + gs2 * t2;
-                            g0 += mb * common;
-                            const double sab = 0.5 * (pa[1] + pb[1]);
-                            g1 += mb * common * (1.5 / sab);  // d sigma_ab^3 / d sigma_a = 1.5 sigma_ab^2
-                            // E1 = sqrt(eps_a eps_b) sigma_ab^3: d/d eps_a = E1 / (2 eps_a); the square root is not
-                            // differentiable at eps_a = 0 (segment '>C<'): that term is left out (the reference's autograd
-                            // returns NaN for every epsilon_k there).  E2 = eps_a eps_b sigma_ab^3.
-                            const double s3k2 = sab * sab * sab * (k1 * k1);
-                            g2 += mb * ((pa[2] != 0.0 ? gs1 * t1 * (0.5 / pa[2]) : 0.0) + gs2 * pb[2] * s3k2);
-                        }
-                        const double ma = ne * pa[0];
-                        lds_add(acc + 8 * a + 0, ne * g0, on);
-                        lds_add(acc + 8 * a + 1, ma * g1, on);
-                        lds_add(acc + 8 * a + 2, ma * g2, on);
-                    }
-                }
-            }
-        }
+        dispersion_sums(gA, gB, ph0, ph1, row, tb, acc, rT, wrow, live);
         // bonds (:156-165): a_hc = -sum rho_i n ln g(c d_ab), g = 1/(1-z3) + 3 c d_ab + 2 (c d_ab)^2 (1 - z3)
 #pragma unroll
         for (int mi = 0; mi < 2; mi++) {
@@ -655,7 +676,7 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
                     const Q1 cd = pcc[pt] * dab;
                     const Q1 g = pz3m1[pt] + 3.0 * cd + 2.0 * ((cd * cd) * pomz[pt]);
                     const Q1 x = (pr[pt][mi] * (-cnt)) * ((pcc[pt] * (3.0 + 4.0 * (cd * pomz[pt]))) * d_recip(g));
-                    gd += dot_q(x, pt);
+                    gd += probe.dot_q(x, pt);
                 }
                 gd *= wrow;
                 const int a = row[32 + mi * GC_MAXE + e], b = row[48 + mi * GC_MAXE + e];
@@ -678,8 +699,11 @@ __global__ __launch_bounds__(BLOCK) void k_gc_segment_gradient(const GcGradArgs 
     }
 }
 
-template <int MODE, int BLOCK>
-static int launch_gc_gradient_block(const GcGradArgs& a, size_t lds, void* stream, const char* what) {
+// one launch per mode: the persistent grid of GS_GRID * GSBLOCK / BLOCK workgroups (682 of 192 threads, 512 of 256) or one per tile
+template <int MODE>
+static int launch_gc_gradient(const GcGradArgs& a, void* stream, const char* what) {
+    constexpr int BLOCK = GsBlock<MODE>::value;
+    const size_t lds = gs_lds_bytes(a.S, BLOCK, MODE);
     const int64_t tiles = (a.n + BLOCK - 1) / BLOCK;
     const int64_t cap = (int64_t)GS_GRID * GSBLOCK / BLOCK;
     const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
@@ -693,35 +717,9 @@ static int launch_gc_gradient_block(const GcGradArgs& a, size_t lds, void* strea
     if (e != hipSuccess) return fail(what, e);
     return 0;
 }
-
-template <int MODE>
-static int launch_gc_gradient_mode(const GcGradArgs& a, void* stream, const char* what) {
-    auto lds_of = [&](int block) { return gc_lds_bytes(a.S, block, GsPerThread<MODE>::value + GC_ROW_LDS_DOUBLES) + sizeof(double) * a.S * 8; };
-    constexpr size_t LDS_CU = 160 * 1024;
-    if (lds_of(256) <= LDS_CU) return launch_gc_gradient_block<MODE, 256>(a, lds_of(256), stream, what);
-    if (lds_of(192) <= LDS_CU) return launch_gc_gradient_block<MODE, 192>(a, lds_of(192), stream, what);
-    return launch_gc_gradient_block<MODE, GSBLOCK>(a, lds_of(GSBLOCK), stream, what);
-}
 }  // namespace
 
 extern "C" {
-
-// LDS of a workgroup: table + gradient accumulator + per thread: bond diameters 2*MAXE doubles, the dual model's diameters
-// 2*MAXE*(1+CHUNK) / the coefficient adjoints, the row bytes.  The kernel holds a full register file per wave and waits mostly
-// for its own stack frame, so the number of resident waves is what counts (measured: one wave per CU 6.6 ms, two 3.8 ms per 1e6
-// rows): a workgroup of several waves shares ONE copy of the table.  launch_gc_gradient_mode takes the largest of 256, 192 and
-// 64 threads whose request stays within the CU's 160 KB, and for the table sizes the ABI admits (S <= 32) that is one branch per
-// mode:
-//   MODE 0 and MODE 2 (bubble / dew, 88 doubles per thread): 24 S^2 + 128 S + 704 BLOCK bytes.  256 threads need 180 224 B before the table
-//     and never fit; 192 threads fit for every S (S = 22: 149 KB; S = 32: 163 840 B, exactly the CU's LDS), so the tile is 192
-//     rows and the 64-thread branch (one table per wave, two workgroups per CU at S = 22) is never reached;
-//   MODE 1 (VJP of `derivatives`, 59 doubles per thread): 256 threads fit for every S (S = 32: 149 504 B), so neither the 192- nor
-//     the 64-thread branch is reached.
-// The unreachable branches are kept for a larger table limit.  (tests/test_gc_point_grad_gpu.py, tests/test_gc_state_gpu.py)
-static int launch_gc_gradient(int mode, const GcGradArgs& a, void* stream, const char* what) {
-    if (mode == 2) return launch_gc_gradient_mode<2>(a, stream, what);
-    return mode == 0 ? launch_gc_gradient_mode<0>(a, stream, what) : launch_gc_gradient_mode<1>(a, stream, what);
-}
 
 int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                             const double* rho4, int64_t n, const double* gout, double* grad_seg, const int32_t* order,
@@ -732,7 +730,7 @@ int pcs_gc_segment_gradient(int dew, const double* table, int S, const uint8_t* 
     GcGradArgs a{};
     a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
     a.gout = gout; a.grad_seg = grad_seg; a.order = order;
-    return launch_gc_gradient(0, a, stream, "k_gc_segment_gradient launch");
+    return launch_gc_gradient<0>(a, stream, "k_gc_segment_gradient launch");
 }
 
 int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
@@ -749,7 +747,7 @@ int pcs_gc_point_segment_gradient(int dew, const double* table, int S, const uin
     GcGradArgs a{};
     a.dew = dew; a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho4; a.n = n;
     a.gout = gout_p; a.gout_y = gout_y; a.grad_seg = grad_seg; a.order = order;
-    return launch_gc_gradient(2, a, stream, "k_gc_point_segment_gradient launch");
+    return launch_gc_gradient<2>(a, stream, "k_gc_point_segment_gradient launch");
 }
 
 int pcs_gc_derivatives_vjp(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
@@ -761,7 +759,7 @@ int pcs_gc_derivatives_vjp(const double* table, int S, const uint8_t* rows, cons
     GcGradArgs a{};
     a.table = table; a.S = S; a.rows = rows; a.phi = phi; a.temp = temp; a.rho = rho; a.n = n;
     a.g_a = g_a; a.g_p = g_p; a.g_mu = g_mu; a.g_v = g_v; a.grad_seg = grad_seg; a.jac9 = jac9; a.agg = agg; a.order = order;
-    return launch_gc_gradient(1, a, stream, "k_gc_derivatives_vjp launch");
+    return launch_gc_gradient<1>(a, stream, "k_gc_derivatives_vjp launch");
 }
 
 }  // extern "C"

@@ -118,7 +118,7 @@ __device__ __attribute__((noinline)) R gc_a_tangent(const GcCoef<G>& c, const R&
     return gc_a<G, R>(c, r0, r1);
 }
 
-inline size_t gc_lds_bytes(int S, int block, int per_thread_doubles) {
+constexpr size_t gc_lds_bytes(int S, int block, int per_thread_doubles) {
     return sizeof(double) * ((size_t)(S * 8 + 3 * S * S) + (size_t)per_thread_doubles * block);
 }
 

@@ -21,10 +21,10 @@ Bars, all from the referee alone: max(1e-10, 10 e) with e = the referee's fp64 r
 the four k_ab records per class sum), and per table column max(1e-10, 10 seg_self_error) with the referee's measured difference
 between two Richardson extrapolations.  Measured on an MI355X: see the tests' docstrings.
 
-Launch geometry of MODE 0 (launch_gc_gradient_mode<0>): the workgroup needs 24 S^2 + 128 S + 704 BLOCK bytes of LDS
+Launch geometry of MODE 0 (launch_gc_gradient<0>, GsBlock<0>): the workgroup needs 24 S^2 + 128 S + 704 BLOCK bytes of LDS
 (table 8 (8 S + 3 S^2), accumulator 64 S, and 16 + 61 + 11 = 88 doubles per thread).  BLOCK = 256 needs at least 180 224 B and never
-fits the 163 840 B of a CU; BLOCK = 192 fits for every admissible S, so the tile is 192 rows for every table and the 64-thread
-branch is never taken; at S = 32 the request is exactly 163 840 B, the whole LDS of a CU.  The persistent grid is capped at
+fits the 163 840 B of a CU; BLOCK = 192 fits for every admissible S, so the tile is 192 rows for every table
+(GsBlock<0>, held by a static_assert); at S = 32 the request is exactly 163 840 B, the whole LDS of a CU.  The persistent grid is capped at
 GS_GRID * GSBLOCK / 192 = 682 workgroups, so the tile loop wraps above 130 944 rows.
 
 Sensitivity, tried on a scratch build and not kept: see test_segment_gradient_vs_exact_gradient."""
@@ -337,7 +337,7 @@ def test_table_size_does_not_change_the_point_gradient(amd, oracle, name, dew):
 
     LDS of k_gc_segment_gradient<0, BLOCK>: 24 S^2 + 128 S + 704 BLOCK bytes.  BLOCK = 192 for every S (256 needs 180 224 B
     before the table): S = 6: 136 800 B, S = 23: 150 808 B, S = 32: 163 840 B -- exactly the LDS of a CU, accepted by the `<=`
-    of launch_gc_gradient_mode and by the runtime.  k_gc_point_jacobian (BLOCK 256,24 S^2 + 64 S + 120 832 B) takes 147 456 B at S = 32;
+    of the static_assert behind GsBlock and by the runtime.  k_gc_point_jacobian (BLOCK 256,24 S^2 + 64 S + 120 832 B) takes 147 456 B at S = 32;
     neither kernel nor the solver had run at S = 32.  What the tables change is the LDS layout and the segment indices, not the
     result: status is equal, p, rho4, jac and agg agree with the full table to 1e-12 relative, the grad_seg rows of the shared
     segments to 1e-12 of the column scale, and the rows of unused and padded segments are exactly 0.

@@ -315,14 +315,14 @@ def test_table_size_selects_the_block_but_not_the_result(amd, table, big):
     segments it uses, in file order, (b) the full table, S = 23, (c) the full table padded to S = 32 with renamed copies of
     existing segments that no molecule uses.
 
-    Block size of k_gc_segment_gradient<1, BLOCK> (launch_gc_gradient_mode<1>): the workgroup needs
+    Block size of k_gc_segment_gradient<1, BLOCK> (launch_gc_gradient<1>, GsBlock<1>): the workgroup needs
     8 * (8 S + 3 S^2 + 59 * BLOCK) + 64 S bytes of LDS (gc_lds_bytes with 48 + 11 doubles per thread, plus the [S,8]
-    accumulator), and the largest BLOCK of 256, 192, 64 that stays within 160 KB is taken:
+    accumulator), and BLOCK is GsBlock<1> = 256, held to the 160 KB of a CU at S = 32 by a static_assert:
       S =  6: 122 464 B -> BLOCK 256;   S = 23: 138 416 B -> BLOCK 256;   S = 32: 149 504 B -> BLOCK 256.
-    S = 32 is the largest table the ABI admits, so the VJP runs at BLOCK = 256 for EVERY table: its 192- and 64-thread
-    branches cannot be reached, and no choice of S makes two different block sizes run.  (The bubble / dew gradient, MODE 0,
-    needs 88 doubles per thread: there BLOCK = 256 never fits and BLOCK = 192 always does -- exactly 160 KB at S = 32 -- so the
-    64-thread branch serves neither mode; tests/test_gc_point_grad_gpu.py.)  What the three tables do change is the LDS layout (table stride S, offset of the
+    S = 32 is the largest table the ABI admits, so the VJP runs at BLOCK = 256 for EVERY table (its
+    only instantiation), and no choice of S makes two different block sizes run.  (The bubble / dew gradient, MODE 0,
+    needs 88 doubles per thread: there BLOCK = 256 never fits and BLOCK = 192 always does -- exactly 160 KB at S = 32;
+    tests/test_gc_point_grad_gpu.py.)  What the three tables do change is the LDS layout (table stride S, offset of the
     accumulator, of the bond area and of the rows) and the segment indices.
 
     Forward outputs, jac9 and agg agree across the tables to 1e-12 relative (measured: bit-identical), the grad_seg rows of the
