@@ -82,7 +82,7 @@ def _stale():
 
 
 def _parse_resources(text):
-    """kernel-resource-usage remarks of one hipcc run -> {mangled name: {vgpr, agpr, scratch, occupancy}}"""
+    """kernel-resource-usage remarks of one hipcc run -> {mangled name: {vgpr, agpr, scratch, occupancy, lds}}"""
     import re
 
     out, cur = {}, None
@@ -94,7 +94,8 @@ def _parse_resources(text):
         if cur is None:
             continue
         for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("agpr", r"remark:\s+AGPRs: (\d+)"),
-                         ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
+                         ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"),
+                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
             m = re.search(pat, line)
             if m:
                 cur[key] = int(m.group(1))

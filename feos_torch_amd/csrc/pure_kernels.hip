@@ -69,6 +69,43 @@ constexpr int K1_BINS = 4;
 // 0.834 ms at 512, 1.014 ms at 1024; the two barriers and the serial straggler wave cost more than the 1.4 iterations per
 // wave they save.  Removed.)
 
+// Staging of k_pure_vle_ordered: position pos of the batch holds row order[pos] (a tile-local permutation as
+// pcs_pure_row_order writes it; a scheduling hint, every row's bits are the same wherever it is solved).  The double2 at tile
+// index idx2 comes from the row at position row0 + (idx2 >> 2): four neighbouring lanes read one whole 64-byte row.  Every
+// entry is bounded by n before it is an index (a foreign or stale array must not fault; an entry out of range stands for
+// its own position); positions past n clamp to position n - 1 and store nothing.  The workgroups of a tile share an XCD
+// (bijective swizzle: hardware workgroup b runs on XCD b % 8 and takes the b / 8-th of that XCD's contiguous share of the
+// grid), so that a tile's lines are fetched into one L2, its scattered stores merge there, and every XCD sees every class --
+// with the plain mapping workgroup k of every 8-workgroup stretch of a class-ordered tile lands on the same XCD and the XCDs
+// that only ever get polar + associating rows set the launch's time (measured on host-permuted input: 0.92 of the unsorted
+// batch without the grouping, 1.07-1.18 with it).
+// -> the row of lane t, -1 for a lane past n; its parameters and T are staged at lds[t * ROW_PAD], behind the barrier.
+__device__ __forceinline__ int64_t ordered_stage(const double* __restrict__ params, const double* __restrict__ temp, int64_t n,
+                                                 const int32_t* __restrict__ order, double* lds) {
+    const int t = threadIdx.x;
+    const unsigned b = blockIdx.x, nwg = gridDim.x, xcd = b % 8u, q = nwg / 8u, rem = nwg % 8u;
+    const unsigned wg = (xcd < rem ? xcd * (q + 1u) : rem * (q + 1u) + (xcd - rem) * q) + b / 8u;
+    const int64_t row0 = (int64_t)wg * BLOCK;
+    auto row_at = [=](int64_t pos) -> int64_t {
+        if (pos > n - 1) pos = n - 1;
+        const int64_t r = order[pos];
+        return (r >= 0 && r < n) ? r : pos;
+    };
+    const double2* src = reinterpret_cast<const double2*>(params);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int idx2 = t + k * BLOCK;
+        const int r = idx2 >> 2, c2 = idx2 & 3;
+        const double2 v = src[row_at(row0 + r) * 4 + c2];
+        lds[r * ROW_PAD + 2 * c2] = v.x;
+        lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
+    }
+    const int64_t i = row_at(row0 + t);
+    lds[t * ROW_PAD + 8] = temp[i];
+    __syncthreads();
+    return row0 + t < n ? i : -1;
+}
+
 // Bucket key of a staged row: model class (which branches of the Helmholtz energy the row needs) in
 // Gray order none, polar, polar+assoc, assoc -- neighbouring buckets share a branch.  Lanes of one
 // wave then mostly run the same branches.  (A second key, a coarse reduced temperature as predictor of
@@ -87,16 +124,36 @@ __device__ __forceinline__ int k1_bucket(const double* row) {
 // appended with bit 31 set (k_pure_vle_fallback takes them), rows for the robust pass without.
 // POLISH (with LITE): the densities are handed out (rho_eq / rho_vl) and take the exact Newton update of vle_lite_finish<true>
 // RHO (with LITE, without POLISH; k_pure_vle_rho): rho_vl is handed out next to an unchanged p_sat (vle_polish_densities)
-template <bool LITE, bool POLISH, bool RHO>
+// ORDERED (with LITE, without POLISH and RHO; k_pure_vle_ordered): the rows come in the caller's tile-local order
+// (pcs_pure_row_order), lane t solves the row at position t of it and nothing is sorted here: see ordered_stage.
+template <bool LITE, bool POLISH, bool RHO, bool ORDERED = false>
 __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
                                                     const double* __restrict__ temp, int64_t n,
                                                     double* __restrict__ p_sat, double* __restrict__ rho_eq,
                                                     double* __restrict__ rho_vl, uint8_t* __restrict__ status,
-                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry) {
+                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry,
+                                                    const int32_t* __restrict__ order = nullptr) {
     __shared__ double lds[BLOCK * ROW_PAD];  // 8 parameters + T per row
     __shared__ int perm[BLOCK];
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
+    if constexpr (ORDERED) {
+        const int64_t i = ordered_stage(params, temp, n, order, lds);
+        VleResult res;
+        const double T = lds[t * ROW_PAD + 8];
+        const int st = vle_fast_lite<POLISH, RHO>(&lds[t * ROW_PAD], T, res);
+        if (i < 0) return;
+        if (st == ST_OK) {
+            if (p_sat) p_sat[i] = res.p_star * T * P_UNIT;
+            if (iters) iters[i] = res.iters;
+            status[i] = 0;
+        } else {
+            status[i] = 1;  // provisional; a later pass overwrites it
+            const int slot = atomicAdd(&retry[0], 1);
+            if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)((uint32_t)i | (st == ST_FALLBACK ? 0x80000000u : 0u));
+        }
+        return;
+    }
     const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
     // cooperative, coalesced staging as stage_rows (pure_stage.hpp), plus T (rows past n clamp to row n-1; never stored).  Written out,
     // like the result stores below: behind a shared helper the compiler schedules these four kernels differently
@@ -174,6 +231,80 @@ __global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_rho(const dou
                                                     double* __restrict__ rho_vl, uint8_t* __restrict__ status,
                                                     int32_t* __restrict__ iters, int32_t* __restrict__ retry) {
     pure_vle_rows<true, false, true>(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry);
+}
+
+// the pressure-only kernel on rows in a reusable tile-local order: p_sat, status and the list as k_pure_vle<true, false>
+// (the list's entries in another sequence), no counting sort, class- and tau-uniform waves from a domain of ORDER_TILE rows
+__global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_ordered(const double* __restrict__ params,
+                                                    const double* __restrict__ temp, int64_t n,
+                                                    double* __restrict__ p_sat, uint8_t* __restrict__ status,
+                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry,
+                                                    const int32_t* __restrict__ order) {
+    pure_vle_rows<true, false, false, true>(params, temp, n, p_sat, nullptr, nullptr, status, iters, retry, order);
+}
+
+// The order k_pure_vle_ordered consumes: one workgroup per tile of ORDER_TILE rows, counting sort in LDS by
+// (class in k1_bucket's Gray order, tau bin); order_out[tile] is a permutation of the tile's row indices, the sequence inside
+// a bucket is whatever the LDS atomics give.  tau = T / (1.28 m^0.45 eps) in fp32, the reduced temperature the fp32
+// pre-solve's evaluation and iteration counts follow; ORDER_TAU_BINS equal bins over the range of tau in the tile itself
+// (a first pass takes its minimum and maximum in LDS), so a data set with a narrow or shifted temperature range keeps all its
+// bins; tau is held to [0, ORDER_TAU_CAP] (NaN counts as 0) so that an invalid row cannot stretch the range without bound.
+// Tile size and bin count from the host-permuted ceiling measurement (scripts/dev/tile_order_ab.py):
+// 16384 rows, 8 bins.
+constexpr int ORDER_TILE = 16384;
+constexpr int ORDER_TAU_BINS = 8;
+constexpr int ORDER_BINS = K1_BINS * ORDER_TAU_BINS;
+constexpr float ORDER_TAU_CAP = 2.0f;
+static_assert(ORDER_TILE % BLOCK == 0 && ORDER_BINS <= BLOCK && ORDER_BINS <= 256, "one key byte per row, one lane per bin");
+__device__ __forceinline__ float order_tau(const double* row, double T) {
+    const float tau = (float)T / (1.28f * (float)row[2] * __powf((float)row[0], 0.45f));
+    return fminf(fmaxf(tau, 0.0f), ORDER_TAU_CAP);  // fmaxf(NaN, 0) = 0
+}
+__global__ __launch_bounds__(BLOCK) void k_pure_row_order(const double* __restrict__ params, const double* __restrict__ temp,
+                                                          int64_t n, int32_t* __restrict__ order_out) {
+    __shared__ uint8_t keys[ORDER_TILE];
+    __shared__ int bins[ORDER_BINS];
+    __shared__ int range[2];  // bits of the smallest / largest tau of the tile: non-negative floats order as their bits do
+    const int t = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * ORDER_TILE;
+    const int count = (int)min((int64_t)ORDER_TILE, n - tile0);
+    if (t < ORDER_BINS) bins[t] = 0;
+    if (t == 0) {
+        range[0] = __float_as_int(ORDER_TAU_CAP);
+        range[1] = 0;
+    }
+    __syncthreads();
+    {
+        float lo = ORDER_TAU_CAP, hi = 0.0f;
+        for (int j = t; j < count; j += BLOCK) {
+            const float tau = order_tau(params + 8 * (tile0 + j), temp[tile0 + j]);
+            lo = fminf(lo, tau);
+            hi = fmaxf(hi, tau);
+        }
+        atomicMin(&range[0], __float_as_int(lo));
+        atomicMax(&range[1], __float_as_int(hi));
+    }
+    __syncthreads();
+    const float tau_lo = __int_as_float(range[0]), width = __int_as_float(range[1]) - tau_lo;
+    const float per_tau = width > 0.0f ? (float)ORDER_TAU_BINS / width : 0.0f;
+    for (int j = t; j < count; j += BLOCK) {
+        const double* row = params + 8 * (tile0 + j);
+        const int bin = (int)fminf((order_tau(row, temp[tile0 + j]) - tau_lo) * per_tau, (float)(ORDER_TAU_BINS - 1));
+        const int key = k1_bucket(row) * ORDER_TAU_BINS + max(bin, 0);
+        keys[j] = (uint8_t)key;
+        atomicAdd(&bins[key], 1);
+    }
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int b = 0; b < ORDER_BINS; b++) {
+            const int c = bins[b];
+            bins[b] = acc;
+            acc += c;
+        }
+    }
+    __syncthreads();
+    for (int j = t; j < count; j += BLOCK) order_out[tile0 + atomicAdd(&bins[keys[j]], 1)] = (int32_t)(tile0 + j);
 }
 #endif
 
@@ -411,13 +542,13 @@ int launch_pure_liquid_density(const double* params, const double* temp, const d
 #if PCS_PURE_PART == 1
 extern "C" {
 
-int pcs_abi_version(void) { return 115; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+int pcs_abi_version(void) { return 116; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
                                             // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp);
                                             // 107: pcs_pure_start_probe; 108: pcs_pure_boiling_temperature, Jacobian selector 3;
                                             // 109: pcs_pure_enthalpy_of_vaporization(_vjp); 110: pcs_mix_bubble_dew_temperature;
                                             // 111: pcs_mix_point_jacobian; 112: pcs_gc_bubble_dew_temperature;
                                             // 113: pcs_gc_point_jacobian, pcs_gc_point_segment_gradient; 114: pcs_mix_density;
-                                            // 115: pcs_gc_density
+                                            // 115: pcs_gc_density; 116: pcs_pure_row_order, pcs_pure_vle_fast_ordered
 
 const char* pcs_last_error(void) { return g_err; }
 
@@ -492,6 +623,26 @@ int pcs_pure_vapor_pressure(const double* params, const double* temp, int64_t n,
 int pcs_pure_vle_fast(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                       double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
     return pure_vle_stages(VLE_STAGE_FAST, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
+}
+
+int pcs_pure_row_order(const double* params, const double* temp, int64_t n, int32_t* order_out, void* stream) {
+    if (int e = enter(n, params && temp && order_out, "pcs_pure_row_order: null required pointer"); e != GO_ON) return e;
+    hipLaunchKernelGGL(k_pure_row_order, dim3(grid_for(n, ORDER_TILE)), dim3(BLOCK), 0, as_stream(stream), params, temp, n, order_out);
+    return launched("k_pure_row_order launch");
+}
+
+// stage 1 of the pressure-only solve on rows in the order of pcs_pure_row_order: reset, k_pure_vle_ordered, fallback
+int pcs_pure_vle_fast_ordered(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq, double* rho_vl,
+                              uint8_t* status, int32_t* iters, void* workspace, const int32_t* order, void* stream) {
+    if (int e = enter(n, params && temp && status && workspace && order, "pcs_pure_vle_fast_ordered: null required pointer"); e != GO_ON) return e;
+    if (rho_eq || rho_vl) return fail_msg("pcs_pure_vle_fast_ordered", "pressure-only form: rho_eq and rho_vl must be null");
+    int32_t* retry = static_cast<int32_t*>(workspace);
+    hipStream_t s = as_stream(stream);
+    if (int ez = zero_ints(retry, 1, s)) return ez;
+    hipLaunchKernelGGL(k_pure_vle_ordered, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, params, temp, n, p_sat, status, iters, retry, order);
+    hipLaunchKernelGGL(k_pure_vle_fallback, dim3(FALLBACK_GRID), dim3(64), 0, s, params, temp, p_sat, nullptr, nullptr, status, iters,
+                       retry, n);
+    return launched("k_pure_vle_ordered launch");
 }
 
 int pcs_pure_vle_retry(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,

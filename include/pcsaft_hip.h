@@ -72,6 +72,24 @@ int pcs_pure_vle_retry(const double* params, const double* temp, int64_t n, doub
                        double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream);
 
 /*
+ * A reusable row order for the pressure-only fast stage (ABI 116).
+ *   pcs_pure_row_order         writes order_out (int32[n]): the batch is cut into tiles of 16384 consecutive rows (the last one
+ *                              may be short) and the entries of a tile are a permutation of that tile's row indices, ordered
+ *                              by model class (none, polar, polar + associating, associating) and, inside a class, by a bin
+ *                              of the reduced temperature T / (1.28 m^0.45 eps).  One kernel, no host synchronisation.
+ *   pcs_pure_vle_fast_ordered  pcs_pure_vle_fast in its pressure-only form (rho_eq and rho_vl must be null) with lane t of
+ *                              the kernel solving row order[t]: waves then hold rows of one class and similar iteration counts.
+ * The order is a scheduling hint: rows are independent, so p_sat, status and the set of listed rows are bit for bit those
+ * of pcs_pure_vle_fast whatever permutation is passed -- an order built from other parameters or temperatures (an earlier
+ * step of a fit) costs speed only.  It must be a permutation of 0..n-1 for every row to be solved; entries are bounded by
+ * n on the device, so a foreign array cannot fault.  pcs_pure_vle_retry follows as after pcs_pure_vle_fast.
+ */
+int pcs_pure_row_order(const double* params, const double* temp, int64_t n, int32_t* order_out, void* stream);
+int pcs_pure_vle_fast_ordered(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
+                              double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, const int32_t* order,
+                              void* stream);
+
+/*
  * pcs_pure_vle with the all-fp64 main kernel (fp64 value / first / second derivative in every Newton iteration after the
  * fp32 start) whatever the outputs -- the validation twin of pcs_pure_vle: same arguments, same results to ~1e-11.
  */

@@ -51,13 +51,21 @@ def short(k):
     return k.split("(")[0][:60]
 
 
-def is_headline(k):
+def is_plain_headline(k):
     return "k_pure_vle<true, false>" in k or "k_pure_vle<true>" in k or "k_pure_vle<(bool)1, (bool)0>" in k
+
+
+ORDERED = False  # set below: the profiled bench ran k_pure_vle_ordered (a default PureVlePlan keeps a row order)
+
+
+def is_headline(k):
+    return "k_pure_vle_ordered" in k if ORDERED else is_plain_headline(k)
 
 
 stats = max(glob.glob(os.path.join(src, "trace", "*", "*_kernel_stats.csv")), key=os.path.getmtime)  # newest: gpurun merges runs
 shutil.copy(stats, os.path.join(dst, f"{tag}_kernel_stats.csv"))
 rows = list(csv.DictReader(open(stats)))
+ORDERED = any("k_pure_vle_ordered" in r["Name"] for r in rows)
 lines = [f"# rocprofv3 summary `{tag}`", "",
          f"Command (scripts/profile.sh): `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps {STEPS} --warmup {WARMUP} "
          "--no-cpu-baseline --no-extra` (1e7 rows per launch; the driver's step counts), PMC counters in separate passes "
@@ -173,7 +181,7 @@ for k, c in allc.items():
                    "issue_ns": issue_ns, "simd_ns": simd_ns, "frac": frac}
 open(os.path.join(dst, f"{tag}_summary.md"), "w").write("\n".join(lines) + "\n")
 if traffic is not None:
-    out = {"tag": tag, "kernel": "k_pure_vle<true, false>", "rows": 10_000_000, "hbm_bytes_per_launch": traffic,
+    out = {"tag": tag, "kernel": "k_pure_vle_ordered" if ORDERED else "k_pure_vle<true, false>", "rows": 10_000_000, "hbm_bytes_per_launch": traffic,
            "valu_wave_instr_per_launch": valu_instr, "kernel_ms_timed_launches": kernel_ms,
            "formula": "(2*FETCH_SIZE + WRITE_SIZE)*1024, separate --pmc passes, gfx950 FETCH correction"}
     if mix_out:
