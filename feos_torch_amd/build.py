@@ -5,35 +5,6 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpcsaft_hip.so")
-# (source, object, extra flags).  pure_kernels.hip is compiled twice: part 1 with re-association (pressure-only VLE kernel,
-# Jacobians, C ABI), part 2 without (all-fp64 VLE kernel, liquid density): see the head of the file
-SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_PURE_PART=1", "-DPCS_CONST_TABLES"]), ("pure_kernels.hip", "pure_kernels_b.o", ["-DPCS_PURE_PART=2"]),
-           ("pure_robust.hip", "pure_robust.o", []), ("compact_kernels.hip", "compact_kernels.o", []),
-           ("mix_kernels.hip", "mix_kernels.o", []), ("mixn_kernels.hip", "mixn_kernels.o", []),
-           ("gc_kernels.hip", "gc_kernels.o", []), ("gc_gradient.hip", "gc_gradient.o", []),
-           ("stability_kernels.hip", "stability_kernels.o", []),
-           # critical points: strict IEEE semantics like pure_robust.hip (neither RELAXED nor REASSOC), csrc/pure_critical.hpp
-           ("pure_critical.hip", "pure_critical.o", []),
-           # boiling temperatures: strict IEEE as well (bracketing and failure detection), no fp32 pre-solve, csrc/pure_boiling.hpp
-           ("pure_boiling.hip", "pure_boiling.o", []),
-           # enthalpies of vaporization and their saturation-line gradients: strict IEEE, no fp32 pre-solve, csrc/pure_enthalpy.hpp
-           ("pure_enthalpy.hip", "pure_enthalpy.o", []),
-           # bubble / dew temperatures: guarded like mix_kernels.hip (the inner solve is pcs_mix_bubble_dew's), csrc/mix_temperature.hip
-           ("mix_temperature.hip", "mix_temperature.o", []),
-           # pressure + incipient-composition gradients of a bubble / dew point: no flags of its own, in the group of mix_kernels.hip
-           # (whose k_mix_jacobian it stands next to), csrc/mix_incipient.hpp
-           ("mix_incipient.hip", "mix_incipient.o", []),
-           # gc bubble / dew temperatures: guarded like gc_kernels.hip (the cold trial is pcs_gc_bubble_dew's), csrc/gc_temperature.hip
-           ("gc_temperature.hip", "gc_temperature.o", []),
-           # gc pressure + incipient-composition gradients of a bubble / dew point (pcs_gc_jacobian and pcs_gc_point_jacobian, one
-           # kernel template): guarded like gc_kernels.hip, csrc/gc_incipient.hip; the table gradient is gc_gradient.hip's kernel
-           ("gc_incipient.hip", "gc_incipient.o", []),
-           # liquid / vapour densities of binary mixtures at (T, p, x): guarded like mix_kernels.hip (the evaluation is
-           # pcs_mix_derivatives' along the composition line), csrc/mix_density.hpp
-           ("mix_density.hip", "mix_density.o", []),
-           # liquid / vapour densities of gc rows at (T, p, x): guarded like gc_kernels.hip (the evaluation is pcs_gc_derivatives'
-           # along the composition line, the root is mix_density.hpp's), csrc/gc_density.hip
-           ("gc_density.hip", "gc_density.o", [])]
 # -fno-honor-nans/-infinities/-signed-zeros: lets the compiler fold the structural zeros of the dual
 # numbers (0 * x, x + 0); every NaN/inf test in the kernels is a bit test (is_finite_bits), so the
 # failure detection does not depend on IEEE comparison semantics.  Measured on k_pure_vle: x1.065,
@@ -49,17 +20,16 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # REASSOC = -fassociative-math -freciprocal-math (round 3): the compiler may re-associate sums / products and turn x / y into
 # x * (1 / y): k_pure_vle<true> 0.783 -> 0.750 ms per 1e7 rows (x1.044, scripts/dev/ab_bench.py; -ffast-math as a whole gives
 # the same), Jacobian kernels x1.13; the all-fp64 VLE kernel and the liquid-density kernel get SLOWER with it (x0.96, x0.75),
-# hence the two parts.  The explicit fma chains of the logarithm / reciprocal refinements are untouched, and the parity of
+# hence the two pure units.  The explicit fma chains of the logarithm / reciprocal refinements are untouched, and the parity of
 # the kernels against the long-double oracle is unchanged (tests/test_large_parity_gpu.py: 1e-10 on 1e6 rows).
-# -DPCS_CONST_TABLES (part 1 only): polynomial constants of the fp64 logarithm and of the pressure-only fp64 evaluation are read
+# -DPCS_CONST_TABLES (pure_kernels.hip only): polynomial constants of the fp64 logarithm and of the pressure-only fp64 evaluation are read
 # from constant memory into scalar registers instead of being moved into vector registers as literals (dual.hpp, pure_model.hpp):
 # k_pure_vle<true> 0.7388 -> 0.7329 ms per 1e7 rows (scripts/dev/ab_alternate.py).
 # -DPCS_FAST_SQRT: the association square root of the pressure-only fp64 finish from v_rsq_f64 with a coupled refinement instead
 # of the library's (d_sqrt_fin, dual.hpp); without it that call is the library square root (A/B builds).
 RELAXED = ["-fno-honor-nans", "-fno-honor-infinities", "-fno-signed-zeros", "-fno-slp-vectorize", "-DPCS_FAST_RCP", "-DPCS_FAST_LOG",
            "-DPCS_F32_PRESOLVE", "-DPCS_FAST_SQRT"]
-REASSOC = ["-fassociative-math", "-freciprocal-math"]  # part 1 of pure_kernels.hip only
-RELAXED_SOURCES = {"pure_kernels.hip"}
+REASSOC = ["-fassociative-math", "-freciprocal-math"]  # pure_kernels.hip only
 # mixture / gc solver units: the short logarithm and the refined hardware reciprocal in their guarded forms (=2: IEEE
 # results for zero, infinite, NaN and negative arguments, which the solvers' failure detection relies on; dual.hpp).
 # 1e6 rows, MI355X: bubble 3.21 -> 2.92 ms, dew 7.07 -> 6.71 ms.
@@ -67,9 +37,47 @@ RELAXED_SOURCES = {"pure_kernels.hip"}
 # 1.74 ms, gc dew 4.28 -> 4.17 ms, dew unchanged (scripts/dev/ab_mix.py / ab_gc.py); the status masks are identical and the
 # results move by <= 6.4e-13 relative.  NaN / infinity semantics stay IEEE (no -fno-honor-*), which the failure detection needs.
 GUARDED = ["-DPCS_FAST_LOG=2", "-DPCS_FAST_RCP=2", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math"]
-GUARDED_SOURCES = {"mix_kernels.hip", "gc_kernels.hip", "stability_kernels.hip", "mix_temperature.hip", "mix_incipient.hip", "gc_temperature.hip",
-                   "gc_incipient.hip", "mix_density.hip", "gc_density.hip"}  # + the stability analysis (NaN / inf outcomes)
+# (source, object, extra flags, flag groups): a unit is built with FLAGS + its groups + its extra flags (unit_flags); no group
+# means strict IEEE semantics.  The pure path is two relaxed units: pure_kernels.hip with re-association (pressure-only VLE
+# kernels, Jacobians, C ABI), pure_fp64.hip without (all-fp64 VLE kernel, liquid density): see the heads of the files
+SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_CONST_TABLES"], [RELAXED, REASSOC]),
+           ("pure_fp64.hip", "pure_kernels_b.o", [], [RELAXED]),
+           ("pure_robust.hip", "pure_robust.o", [], []), ("compact_kernels.hip", "compact_kernels.o", [], []),
+           ("mix_kernels.hip", "mix_kernels.o", [], [GUARDED]), ("mixn_kernels.hip", "mixn_kernels.o", [], []),
+           ("gc_kernels.hip", "gc_kernels.o", [], [GUARDED]), ("gc_gradient.hip", "gc_gradient.o", [], []),
+           ("stability_kernels.hip", "stability_kernels.o", [], [GUARDED]),
+           # critical points: strict IEEE semantics like pure_robust.hip (neither RELAXED nor REASSOC), csrc/pure_critical.hpp
+           ("pure_critical.hip", "pure_critical.o", [], []),
+           # boiling temperatures: strict IEEE as well (bracketing and failure detection), no fp32 pre-solve, csrc/pure_boiling.hpp
+           ("pure_boiling.hip", "pure_boiling.o", [], []),
+           # enthalpies of vaporization and their saturation-line gradients: strict IEEE, no fp32 pre-solve, csrc/pure_enthalpy.hpp
+           ("pure_enthalpy.hip", "pure_enthalpy.o", [], []),
+           # bubble / dew temperatures: guarded like mix_kernels.hip (the inner solve is pcs_mix_bubble_dew's), csrc/mix_temperature.hip
+           ("mix_temperature.hip", "mix_temperature.o", [], [GUARDED]),
+           # pressure + incipient-composition gradients of a bubble / dew point: no flags of its own, in the group of mix_kernels.hip
+           # (whose k_mix_jacobian it stands next to), csrc/mix_incipient.hpp
+           ("mix_incipient.hip", "mix_incipient.o", [], [GUARDED]),
+           # gc bubble / dew temperatures: guarded like gc_kernels.hip (the cold trial is pcs_gc_bubble_dew's), csrc/gc_temperature.hip
+           ("gc_temperature.hip", "gc_temperature.o", [], [GUARDED]),
+           # gc pressure + incipient-composition gradients of a bubble / dew point (pcs_gc_jacobian and pcs_gc_point_jacobian, one
+           # kernel template): guarded like gc_kernels.hip, csrc/gc_incipient.hip; the table gradient is gc_gradient.hip's kernel
+           ("gc_incipient.hip", "gc_incipient.o", [], [GUARDED]),
+           # liquid / vapour densities of binary mixtures at (T, p, x): guarded like mix_kernels.hip (the evaluation is
+           # pcs_mix_derivatives' along the composition line), csrc/mix_density.hpp
+           ("mix_density.hip", "mix_density.o", [], [GUARDED]),
+           # liquid / vapour densities of gc rows at (T, p, x): guarded like gc_kernels.hip (the evaluation is pcs_gc_derivatives'
+           # along the composition line, the root is mix_density.hpp's), csrc/gc_density.hip
+           ("gc_density.hip", "gc_density.o", [], [GUARDED])]
+# the units of a group, for reading only (no flag is chosen through them); GUARDED includes the stability analysis (NaN / inf outcomes)
+RELAXED_SOURCES = {src for src, _, _, groups in SOURCES if RELAXED in groups}
+GUARDED_SOURCES = {src for src, _, _, groups in SOURCES if GUARDED in groups}
 RESOURCES = os.path.join(HERE, "build", "resources.json")  # per-kernel register / stack report of the last build
+
+
+def unit_flags(entry):
+    """every compiler flag of one entry of SOURCES, in the order of the command line"""
+    _, _, extra, groups = entry
+    return FLAGS + [flag for group in groups for flag in group] + extra
 
 
 def _stale():
@@ -116,10 +124,9 @@ def build(force=False, verbose=False):
     # one hipcc per translation unit in parallel, then link
     objs, procs = [], []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
-    for s, oname, extra in SOURCES:
-        obj = os.path.join(HERE, "build", oname)
-        cmd = (["hipcc"] + FLAGS + (RELAXED if s in RELAXED_SOURCES else []) + (REASSOC if "-DPCS_PURE_PART=1" in extra else [])
-               + (GUARDED if s in GUARDED_SOURCES else []) + extra + ["-c", "-o", obj, os.path.join(CSRC, s)])
+    for entry in SOURCES:
+        obj = os.path.join(HERE, "build", entry[1])
+        cmd = ["hipcc"] + unit_flags(entry) + ["-c", "-o", obj, os.path.join(CSRC, entry[0])]
         if verbose:
             print(" ".join(cmd))
         # the compiler's per-kernel register / stack report is kept next to the objects (tests/test_abi.py guards the

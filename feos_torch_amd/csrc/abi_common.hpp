@@ -56,6 +56,16 @@ inline int launched(const char* what) {
 // workgroups of `block` lanes that cover n rows
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
+// Launch functions the entry points of pure_kernels.hip call in units built with other flags (feos_torch_amd/build.py).
+// pure_robust.hip, strict IEEE semantics: stage 2 of the VLE (k_pure_vle_robust)
+int launch_pure_vle_retry(const double* params, const double* temp, double* p_sat, double* rho_eq, double* rho_vl,
+                          uint8_t* status, int32_t* iters, const int32_t* retry, int64_t n, hipStream_t s);
+// pure_fp64.hip, no re-association: the all-fp64 VLE kernel k_pure_vle<false> and k_pure_liquid_density
+int launch_pure_vle_full(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq, double* rho_vl,
+                         uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s);
+int launch_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n, double* rho_out,
+                               double* rho_root, uint8_t* status, hipStream_t s);
+
 // Device-side counters (retry-list count, work-queue control block) are zeroed by a KERNEL on the call's stream, not by
 // hipMemsetAsync: every operation of a call is then a kernel node of a hipGraph capture.  What round 2's one A/B run shows
 // (profiles/r02_capture_ab.log, scripts/dev/capture_ab.py plants a stale count of 0x7FFFFFF0 before every replay): with this

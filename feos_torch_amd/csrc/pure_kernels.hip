@@ -1,228 +1,27 @@
-// gfx950 kernels + C ABI for the pure-component PC-SAFT path (see include/pcsaft_hip.h).
+// gfx950 kernels + C ABI for the pure-component PC-SAFT path (see include/pcsaft_hip.h).  Launch shape and memory handling:
+// pure_vle_rows.hpp.
 //
-// Launch shape: one state point per lane, 256-thread workgroups (4 waves), grid = ceil(n/256)
-// (>> 256 workgroups at the benchmark sizes, so all 8 XCDs fill; rows are independent, so the
-// round-robin workgroup->XCD placement needs no remapping — there is no shared tile to keep
-// in one L2).  HBM traffic is 81 B per state point against ~1e4 fp64 operations: the kernels
-// are fp64-VALU bound; memory handling only has to be coalesced, which it is:
-//   * the [n,8] AoS parameter rows of a workgroup (16 KB contiguous) are fetched with 16-byte
-//     per-lane loads and staged through LDS (72-byte padded rows, conflict-free ds_read_b64);
-//   * T, p and all outputs are SoA and accessed lane-contiguously.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
+// The pure path is three units (feos_torch_amd/build.py), all but the last with the relaxed floating-point flags:
+//   pure_kernels.hip  (this file) with -fassociative-math -freciprocal-math: the pressure-only VLE kernels (0.783 -> 0.750 ms
+//                     per 1e7 rows, x1.044), the Jacobian kernels (x1.13), fallback, derivatives, their VJP, and the whole C ABI;
+//   pure_fp64.hip     without re-association: the all-fp64 VLE kernel and the liquid-density kernel, which it makes slower;
+//   pure_robust.hip   strict IEEE semantics: stage 2 of the VLE (k_pure_vle_robust).
+// A build-level switch like PCS_FAST_RCP, not an experiment: all units are always built and linked.  The entry points here
+// reach the other two through the launch functions declared in abi_common.hpp.
 #include "../../include/pcsaft_hip.h"
 #include "abi_common.hpp"
-#include "block_order.hpp"
-#include "pure_solver.hpp"
+#include "pure_vle_rows.hpp"
 #include "pure_jacobian.hpp"
-#include "pure_stage.hpp"
 
-// This file is compiled TWICE (feos_torch_amd/build.py), with the same relaxed floating-point flags but
-//   PCS_PURE_PART = 1  with -fassociative-math -freciprocal-math: the pressure-only VLE kernel (0.783 -> 0.750 ms per 1e7 rows,
-//                      x1.044), the Jacobian kernels (x1.13), fallback, derivatives, their VJP, and the whole C ABI;
-//   PCS_PURE_PART = 2  without: the all-fp64 VLE kernel and the liquid-density kernel, which re-association makes SLOWER
-//                      (x0.96; 0.895 -> 1.19 ms: the re-associated expressions cost k_pure_liquid_density its register budget),
-//                      behind two launch functions that part 1 calls.
-// Measured in one process with scripts/dev/ab_bench.py / ab_k2.py / ab_purejac.py (round 3).  A build-level switch like
-// PCS_FAST_RCP, not an experiment: both parts are always built and linked.
-#ifndef PCS_PURE_PART
-#define PCS_PURE_PART 1
-#endif
-
-// stage 2 (k_pure_vle_robust) lives in pure_robust.hip, compiled with strict IEEE semantics
-namespace pcs_abi {
-int launch_pure_vle_retry(const double* params, const double* temp, double* p_sat, double* rho_eq, double* rho_vl,
-                          uint8_t* status, int32_t* iters, const int32_t* retry, int64_t n, hipStream_t s);
-// part 2 of this file
-int launch_pure_vle_full(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq, double* rho_vl,
-                         uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s);
-int launch_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n, double* rho_out,
-                               double* rho_root, uint8_t* status, hipStream_t s);
-}
-#define launch_vle_retry pcs_abi::launch_pure_vle_retry
-
-using namespace pcs;
 using namespace pcs_abi;
 
-#if PCS_PURE_PART == 1
 thread_local char pcs_abi::g_err[256] = "";
-#endif
 
 namespace {
 
 constexpr int BLOCK = STAGE_BLOCK;  // workgroup size, padded row and stage_rows: pure_stage.hpp
 constexpr int ROW_PAD = STAGE_ROW_PAD;
 
-// ------------------------------------------------------------------------------------------
-// K1: pure VLE, fast path.  Rows that need the robust initialisation are appended to
-// retry[1..]; retry[0] is the running count.
-// ------------------------------------------------------------------------------------------
-// waves per SIMD asked of the compiler for the all-fp64 instantiation (p_sat + densities): 210 VGPRs fit two; held to 128
-// (152 spill instructions) four are resident and the kernel is 1.20 -> 0.96 ms per 1e7 rows (three: 1.00 ms)
-constexpr int K1_WAVES = 4;
-constexpr int K1_WAVES_LITE = 4;  // pressure-only instantiation: 122 VGPR, 4 waves per SIMD (without -fno-slp-vectorize: 168 VGPR, 3 waves)
-constexpr int K1_BINS = 4;
-// (Round 2 measured a block-level straggler exchange of the fp32 coupled iteration -- lanes not converged after two iterations
-// parked in LDS and finished together by the first wave: 0.815 ms against 0.797 ms without it at 256 threads per workgroup,
-// 0.834 ms at 512, 1.014 ms at 1024; the two barriers and the serial straggler wave cost more than the 1.4 iterations per
-// wave they save.  Removed.)
-
-// Staging of k_pure_vle_ordered: position pos of the batch holds row order[pos] (a tile-local permutation as
-// pcs_pure_row_order writes it; a scheduling hint, every row's bits are the same wherever it is solved).  The double2 at tile
-// index idx2 comes from the row at position row0 + (idx2 >> 2): four neighbouring lanes read one whole 64-byte row.  Every
-// entry is bounded by n before it is an index (a foreign or stale array must not fault; an entry out of range stands for
-// its own position); positions past n clamp to position n - 1 and store nothing.  The workgroups of a tile share an XCD
-// (bijective swizzle: hardware workgroup b runs on XCD b % 8 and takes the b / 8-th of that XCD's contiguous share of the
-// grid), so that a tile's lines are fetched into one L2, its scattered stores merge there, and every XCD sees every class --
-// with the plain mapping workgroup k of every 8-workgroup stretch of a class-ordered tile lands on the same XCD and the XCDs
-// that only ever get polar + associating rows set the launch's time (measured on host-permuted input: 0.92 of the unsorted
-// batch without the grouping, 1.07-1.18 with it).
-// -> the row of lane t, -1 for a lane past n; its parameters and T are staged at lds[t * ROW_PAD], behind the barrier.
-__device__ __forceinline__ int64_t ordered_stage(const double* __restrict__ params, const double* __restrict__ temp, int64_t n,
-                                                 const int32_t* __restrict__ order, double* lds) {
-    const int t = threadIdx.x;
-    const unsigned b = blockIdx.x, nwg = gridDim.x, xcd = b % 8u, q = nwg / 8u, rem = nwg % 8u;
-    const unsigned wg = (xcd < rem ? xcd * (q + 1u) : rem * (q + 1u) + (xcd - rem) * q) + b / 8u;
-    const int64_t row0 = (int64_t)wg * BLOCK;
-    auto row_at = [=](int64_t pos) -> int64_t {
-        if (pos > n - 1) pos = n - 1;
-        const int64_t r = order[pos];
-        return (r >= 0 && r < n) ? r : pos;
-    };
-    const double2* src = reinterpret_cast<const double2*>(params);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx2 = t + k * BLOCK;
-        const int r = idx2 >> 2, c2 = idx2 & 3;
-        const double2 v = src[row_at(row0 + r) * 4 + c2];
-        lds[r * ROW_PAD + 2 * c2] = v.x;
-        lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
-    }
-    const int64_t i = row_at(row0 + t);
-    lds[t * ROW_PAD + 8] = temp[i];
-    __syncthreads();
-    return row0 + t < n ? i : -1;
-}
-
-// Bucket key of a staged row: model class (which branches of the Helmholtz energy the row needs) in
-// Gray order none, polar, polar+assoc, assoc -- neighbouring buckets share a branch.  Lanes of one
-// wave then mostly run the same branches.  (A second key, a coarse reduced temperature as predictor of
-// the iteration count, measured 0.5-1.5 % slower on a 256-row domain: not used.)
-__device__ __forceinline__ int k1_bucket(const double* row) {
-    const bool polar = row[3] != 0.0;
-    const bool assoc = (row[4] != 0.0) && (row[6] != 0.0 || row[7] != 0.0);
-    return polar ? (assoc ? 2 : 1) : (assoc ? 3 : 0);
-}
-
-// The 256 staged rows of the workgroup are bucketed (LDS counting sort; the order inside a bucket is
-// irrelevant) and lane t solves the row at sorted position t.  A larger bucketing domain (4 tiles per
-// workgroup) measured only 2-3 % faster and costs either LDS occupancy or a non-inlined call per
-// tile whose callee-saved registers go through scratch (3.8 GB of HBM writes per 1e7 rows): not used.
-// LITE (pressure-only output, fp32 pre-solve available): vle_fast_lite; rows without a usable fp32 result are
-// appended with bit 31 set (k_pure_vle_fallback takes them), rows for the robust pass without.
-// POLISH (with LITE): the densities are handed out (rho_eq / rho_vl) and take the exact Newton update of vle_lite_finish<true>
-// RHO (with LITE, without POLISH; k_pure_vle_rho): rho_vl is handed out next to an unchanged p_sat (vle_polish_densities)
-// ORDERED (with LITE, without POLISH and RHO; k_pure_vle_ordered): the rows come in the caller's tile-local order
-// (pcs_pure_row_order), lane t solves the row at position t of it and nothing is sorted here: see ordered_stage.
-template <bool LITE, bool POLISH, bool RHO, bool ORDERED = false>
-__device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
-                                                    const double* __restrict__ temp, int64_t n,
-                                                    double* __restrict__ p_sat, double* __restrict__ rho_eq,
-                                                    double* __restrict__ rho_vl, uint8_t* __restrict__ status,
-                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry,
-                                                    const int32_t* __restrict__ order = nullptr) {
-    __shared__ double lds[BLOCK * ROW_PAD];  // 8 parameters + T per row
-    __shared__ int perm[BLOCK];
-    __shared__ int bins[K1_BINS];
-    const int t = threadIdx.x;
-    if constexpr (ORDERED) {
-        const int64_t i = ordered_stage(params, temp, n, order, lds);
-        VleResult res;
-        const double T = lds[t * ROW_PAD + 8];
-        const int st = vle_fast_lite<POLISH, RHO>(&lds[t * ROW_PAD], T, res);
-        if (i < 0) return;
-        if (st == ST_OK) {
-            if (p_sat) p_sat[i] = res.p_star * T * P_UNIT;
-            if (iters) iters[i] = res.iters;
-            status[i] = 0;
-        } else {
-            status[i] = 1;  // provisional; a later pass overwrites it
-            const int slot = atomicAdd(&retry[0], 1);
-            if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)((uint32_t)i | (st == ST_FALLBACK ? 0x80000000u : 0u));
-        }
-        return;
-    }
-    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    // cooperative, coalesced staging as stage_rows (pure_stage.hpp), plus T (rows past n clamp to row n-1; never stored).  Written out,
-    // like the result stores below: behind a shared helper the compiler schedules these four kernels differently
-    {
-        const double2* src = reinterpret_cast<const double2*>(params);
-        const int64_t last2 = n * 4 - 1;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int idx2 = t + k * BLOCK;
-            int64_t g = row0 * 4 + idx2;
-            if (g > last2) g = last2 - 3 + (idx2 & 3);
-            double2 v = src[g];
-            int r = idx2 >> 2, c2 = idx2 & 3;
-            lds[r * ROW_PAD + 2 * c2] = v.x;
-            lds[r * ROW_PAD + 2 * c2 + 1] = v.y;
-        }
-        const int64_t g = row0 + t;
-        lds[t * ROW_PAD + 8] = temp[g < n ? g : n - 1];
-        block_order_reset<K1_BINS>(bins);
-    }
-    __syncthreads();
-    block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
-
-    const int r = perm[t];
-    const int64_t i = row0 + r;
-    const bool live = i < n;
-    double par[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) par[q] = lds[r * ROW_PAD + q];
-    const double T = lds[r * ROW_PAD + 8];
-
-    VleResult res;
-    int st;  // every lane of the wave makes the call (its loops end on ballots over the lanes still working)
-    const bool polish_rho = rho_vl != nullptr;  // densities as an output of a solve that stops at the pressure tolerances
-#ifdef PCS_F32_PRESOLVE
-    if (LITE) st = vle_fast_lite<POLISH, RHO>(&lds[r * ROW_PAD], lds[r * ROW_PAD + 8], res);  // the row is re-read from LDS for the fp64 coefficients
-    else st = rho_eq ? vle_fast<true>(par, T, res, 1e-8, TOL_STEP) : vle_fast<true>(par, T, res, TOL_L_P, TOL_V_P, polish_rho);
-#else
-    st = rho_eq ? vle_fast<false>(par, T, res, 1e-8, TOL_STEP) : vle_fast<false>(par, T, res, TOL_L_P, TOL_V_P, polish_rho);
-#endif
-
-    if (!live) return;
-    if (st == ST_OK) {
-        if (p_sat) p_sat[i] = res.p_star * T * P_UNIT;
-        if (rho_eq) rho_eq[i] = res.rho_l * (1.0 / RHO_UNIT);
-        if (rho_vl) {
-            rho_vl[2 * i] = res.rho_v;
-            rho_vl[2 * i + 1] = res.rho_l;
-        }
-        if (iters) iters[i] = res.iters;
-        status[i] = 0;
-    } else {
-        status[i] = 1;  // provisional; a later pass overwrites it
-        const int slot = atomicAdd(&retry[0], 1);
-        // bounded append: a counter that was not reset (stale / foreign workspace) must not send the store out of the list
-        if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)((uint32_t)i | (st == ST_FALLBACK ? 0x80000000u : 0u));  // n < 2^31 checked on the host
-    }
-}
-
-template <bool LITE, bool POLISH = false>
-__global__ __launch_bounds__(BLOCK, LITE ? K1_WAVES_LITE : K1_WAVES) void k_pure_vle(const double* __restrict__ params,
-                                                    const double* __restrict__ temp, int64_t n,
-                                                    double* __restrict__ p_sat, double* __restrict__ rho_eq,
-                                                    double* __restrict__ rho_vl, uint8_t* __restrict__ status,
-                                                    int32_t* __restrict__ iters, int32_t* __restrict__ retry) {
-    pure_vle_rows<LITE, POLISH, false>(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry);
-}
-
-#if PCS_PURE_PART == 1
 // the pressure-only kernel handing out rho_vl (pcs_pure_vapor_pressure with densities): p_sat and status bit for bit as
 // k_pure_vle<true, false>, the densities of the solved rows through vle_polish_densities
 __global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_rho(const double* __restrict__ params,
@@ -306,11 +105,9 @@ __global__ __launch_bounds__(BLOCK) void k_pure_row_order(const double* __restri
     __syncthreads();
     for (int j = t; j < count; j += BLOCK) order_out[tile0 + atomicAdd(&bins[keys[j]], 1)] = (int32_t)(tile0 + j);
 }
-#endif
 
 // Rows of the list with bit 31 set (no usable fp32 pre-solve): the all-fp64 fast path.  Solved rows keep the
 // bit (the robust pass skips them), rows that need the robust pass get it cleared.
-#if PCS_PURE_PART == 1
 constexpr int FALLBACK_GRID = 1024;
 __global__ __launch_bounds__(64) void k_pure_vle_fallback(const double* __restrict__ params, const double* __restrict__ temp,
                                                           double* __restrict__ p_sat, double* __restrict__ rho_eq,
@@ -346,59 +143,6 @@ __global__ __launch_bounds__(64) void k_pure_vle_fallback(const double* __restri
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// K2: liquid density at (T, p)
-// ------------------------------------------------------------------------------------------
-// liquid-density kernel: 204 VGPRs fit two waves per SIMD; held to 168 (52 spill instructions) three: 1.02 -> 0.89 ms per 1e7
-// rows (four, 128 VGPRs: 1.02 ms)
-#endif  // part 1
-
-constexpr int K4_WAVES = 2;  // Jacobian kernels: two (256 VGPRs); held to 168 for three they spill inside the DN<9> pass: 0.89 -> 2.24 ms
-constexpr int K2_WAVES = 3;
-#if PCS_PURE_PART == 2
-__global__ __launch_bounds__(BLOCK, K2_WAVES) void k_pure_liquid_density(const double* __restrict__ params,
-                                                               const double* __restrict__ temp,
-                                                               const double* __restrict__ pressure, int64_t n,
-                                                               double* __restrict__ rho_out,
-                                                               double* __restrict__ rho_root,
-                                                               uint8_t* __restrict__ status) {
-    __shared__ double lds[BLOCK * ROW_PAD];
-    const int64_t row0 = (int64_t)blockIdx.x * BLOCK;
-    // rows of the workgroup bucketed by class as in k_pure_vle (LDS counting sort): a wave mostly runs one set of
-    // branches of the Helmholtz energy
-    __shared__ int perm[BLOCK];
-    __shared__ int bins[K1_BINS];
-    const int t = threadIdx.x;
-    block_order_reset<K1_BINS>(bins);
-    stage_rows(params, n, row0, lds);
-    block_order_sort<K1_BINS>(bins, perm, [=] { return k1_bucket(&lds[t * ROW_PAD]); });
-    const int src = perm[t];
-    double par[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) par[q] = lds[src * ROW_PAD + q];
-    const int64_t i = row0 + src;
-    const bool live = i < n;
-    const int64_t ii = live ? i : n - 1;
-    const double T = temp[ii];
-    const double p_red = pressure[ii] / (T * P_UNIT);  // pcsaft_pure.py:196
-
-    PureCoef<double> c;
-    pure_coef<double>(c, par, T, false);
-    double rho;
-    Eval last;
-    int st = liquid_density_solve(c, p_red, TOL_STEP, rho, last);
-    if (!live) return;
-    // `rho` already carries the final Newton update rho - (p - p_spec)/dp (pcsaft_pure.py:198) taken
-    // at a point whose relative step was <= TOL_STEP, i.e. it is converged to ~1e-11; it is both
-    // the returned property and the density reported as the root.
-    bool ok = (st == ST_OK);
-    if (rho_out) rho_out[i] = ok ? rho * (1.0 / RHO_UNIT) : 0.0;
-    if (rho_root) rho_root[i] = ok ? rho : 0.0;
-    status[i] = ok ? 0 : 1;
-}
-#endif  // part 2
-
-#if PCS_PURE_PART == 1
 // ------------------------------------------------------------------------------------------
 // derivatives (a, p, dp) at given (T, rho)
 // ------------------------------------------------------------------------------------------
@@ -441,6 +185,7 @@ __global__ __launch_bounds__(BLOCK) void k_pure_start_probe(const double* __rest
 // ------------------------------------------------------------------------------------------
 // K4: Jacobian of a property w.r.t. (8 parameters, T, p) at fixed densities
 // ------------------------------------------------------------------------------------------
+constexpr int K4_WAVES = 2;  // Jacobian kernels: two (256 VGPRs); held to 168 for three they spill inside the DN<9> pass: 0.89 -> 2.24 ms
 template <int WHICH>
 __global__ __launch_bounds__(BLOCK, K4_WAVES) void k_pure_jacobian(const double* __restrict__ params,
                                                          const double* __restrict__ temp,
@@ -516,30 +261,8 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives_vjp(const double* __
     if (grad_rho) grad_rho[i] = g[9];
 }
 
-#endif  // part 1
-
 }  // namespace
 
-#if PCS_PURE_PART == 2
-// launch functions of the kernels compiled without re-association (called from part 1)
-namespace pcs_abi {
-int launch_pure_vle_full(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq, double* rho_vl,
-                         uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s) {
-    const unsigned grid = grid_for(n, BLOCK);
-    hipLaunchKernelGGL(k_pure_vle<false>, dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status, iters,
-                       retry);
-    return launched("k_pure_vle launch");
-}
-int launch_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n, double* rho_out,
-                               double* rho_root, uint8_t* status, hipStream_t s) {
-    const unsigned grid = grid_for(n, BLOCK);
-    hipLaunchKernelGGL(k_pure_liquid_density, dim3(grid), dim3(BLOCK), 0, s, params, temp, pressure, n, rho_out, rho_root, status);
-    return launched("k_pure_liquid_density launch");
-}
-}  // namespace pcs_abi
-#endif
-
-#if PCS_PURE_PART == 1
 extern "C" {
 
 int pcs_abi_version(void) { return 116; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
@@ -555,74 +278,79 @@ const char* pcs_last_error(void) { return g_err; }
 // retry list of the pure / gc two-pass schedules (n + 1 ints) or row order + control block of the mixture work queue (n + 64)
 int64_t pcs_workspace_bytes(int64_t n) { return (int64_t)sizeof(int32_t) * (n + 64); }
 
-// stage 1: zero the retry counter and run the fast kernel over all rows
-static int launch_vle_fast(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
-                           double* rho_vl, uint8_t* status, int32_t* iters, int32_t* retry, hipStream_t s,
-                           bool force_lite = false, bool all_fp64 = false) {
-    if (int ez = zero_ints(retry, 1, s)) return ez;
-    const unsigned grid = grid_for(n, BLOCK);
-    // main kernel (lean: rows without an fp32 pre-solve go to the list with bit 31 set) + all-fp64 fallback kernel.
-    //  * pressure only: k_pure_vle<true>, densities converged to ~1e-9 inside the kernel (enough for p*, whose error is of
-    //    second order in them) and not handed out;
-    //  * pcs_pure_vapor_pressure with densities: k_pure_vle_rho, the same solve and the same p_sat bits + the exact Newton
-    //    update of vle_polish_densities on the densities it hands out (the fp32-slope iteration leaves rho_V up to 1.9e-6 off);
-    //  * rho_vl without rho_eq (the Jacobian kernels' input), and everything under all_fp64 (pcs_pure_vle_fp64):
-    //    k_pure_vle<false>, the fp64 D2 iteration from the fp32 pre-solve's start -- one iteration at the pressure
-    //    tolerances, which leaves rho_V up to 5.9e-9 off, + vle_polish_densities when rho_vl is an output: 0.98 -> 1.35 ms
-    //    per 1e7 rows for the second D2 evaluation of both phases;
-    //  * rho_eq requested (tolerance 1e-8 on the liquid step: two D2 iterations of the all-fp64 kernel, 1.55-1.67 ms): the
-    //    pressure-only kernel + the exact Newton update of vle_lite_finish<true> instead, 1.22 ms (round 3).
-    if (all_fp64 || (!rho_eq && rho_vl && !force_lite)) {
-        if (int ef = launch_pure_vle_full(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, s)) return ef;
-    } else if (!rho_eq && rho_vl) {  // pcs_pure_vapor_pressure with densities: the same p_sat bits, rho_vl polished
-        hipLaunchKernelGGL(k_pure_vle_rho, dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status,
-                           iters, retry);
-    } else if (!rho_eq) {
-        hipLaunchKernelGGL((k_pure_vle<true, false>), dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status,
-                           iters, retry);
-    } else {
-        hipLaunchKernelGGL((k_pure_vle<true, true>), dim3(grid), dim3(BLOCK), 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status,
-                           iters, retry);
-    }
-    hipLaunchKernelGGL(k_pure_vle_fallback, dim3(FALLBACK_GRID), dim3(64), 0, s, params, temp, p_sat, rho_eq, rho_vl, status,
-                       iters, retry, n);
-    return launched("k_pure_vle launch");
+// The main kernel of stage 1, and the kinds of entry point that choose among them
+enum class VleKernel { LITE, LITE_POLISH, LITE_RHO, FP64, ORDERED };
+enum class VleEntry { VLE, FP64, VAPOR_PRESSURE, ORDERED };  // pcs_pure_vle(_fast), _vle_fp64, _vapor_pressure, _vle_fast_ordered
+
+// main kernel (lean: rows without an fp32 pre-solve go to the list with bit 31 set) + all-fp64 fallback kernel.
+//  * pressure only: k_pure_vle<true>, densities converged to ~1e-9 inside the kernel (enough for p*, whose error is of
+//    second order in them) and not handed out; on rows in the order of pcs_pure_row_order: k_pure_vle_ordered;
+//  * pcs_pure_vapor_pressure with densities: k_pure_vle_rho, the same solve and the same p_sat bits + the exact Newton
+//    update of vle_polish_densities on the densities it hands out (the fp32-slope iteration leaves rho_V up to 1.9e-6 off);
+//  * rho_vl without rho_eq (the Jacobian kernels' input), and everything of pcs_pure_vle_fp64:
+//    k_pure_vle<false>, the fp64 D2 iteration from the fp32 pre-solve's start -- one iteration at the pressure
+//    tolerances, which leaves rho_V up to 5.9e-9 off, + vle_polish_densities when rho_vl is an output: 0.98 -> 1.35 ms
+//    per 1e7 rows for the second D2 evaluation of both phases;
+//  * rho_eq requested (tolerance 1e-8 on the liquid step: two D2 iterations of the all-fp64 kernel, 1.55-1.67 ms): the
+//    pressure-only kernel + the exact Newton update of vle_lite_finish<true> instead, 1.22 ms (round 3).
+static VleKernel vle_main_kernel(VleEntry entry, bool rho_eq, bool rho_vl) {
+    if (entry == VleEntry::ORDERED) return VleKernel::ORDERED;  // pressure-only form: the entry point refuses densities
+    if (entry == VleEntry::FP64) return VleKernel::FP64;
+    if (rho_eq) return VleKernel::LITE_POLISH;
+    if (!rho_vl) return VleKernel::LITE;
+    return entry == VleEntry::VAPOR_PRESSURE ? VleKernel::LITE_RHO : VleKernel::FP64;
 }
 
-// the pcs_pure_vle* family: stage 1 (fast kernel + fallback) and / or stage 2 (robust pass over the list in the workspace)
+// the pcs_pure_vle* family: stage 1 (zero the retry counter, main kernel over all rows, fallback over the list) and / or
+// stage 2 (robust pass over the list in the workspace)
 enum : int { VLE_STAGE_FAST = 1, VLE_STAGE_RETRY = 2 };
-static int pure_vle_stages(int stages, const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
-                           double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream,
-                           bool force_lite = false, bool all_fp64 = false) {
+static int pure_vle_stages(int stages, VleEntry entry, const double* params, const double* temp, int64_t n, double* p_sat,
+                           double* rho_eq, double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream,
+                           const int32_t* order = nullptr) {
     if (int e = enter(n, params && temp && status && workspace, "pcs_pure_vle: null required pointer"); e != GO_ON) return e;
     int32_t* retry = static_cast<int32_t*>(workspace);
     hipStream_t s = as_stream(stream);
-    if (stages & VLE_STAGE_FAST)
-        if (int e = launch_vle_fast(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, s, force_lite, all_fp64)) return e;
-    if (stages & VLE_STAGE_RETRY) return launch_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters, retry, n, s);
+    if (stages & VLE_STAGE_FAST) {
+        if (int ez = zero_ints(retry, 1, s)) return ez;
+        const dim3 grid(grid_for(n, BLOCK)), block(BLOCK);
+        const VleKernel main = vle_main_kernel(entry, rho_eq, rho_vl);
+        switch (main) {
+            case VleKernel::LITE: hipLaunchKernelGGL((k_pure_vle<true, false>), grid, block, 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry); break;
+            case VleKernel::LITE_POLISH: hipLaunchKernelGGL((k_pure_vle<true, true>), grid, block, 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry); break;
+            case VleKernel::LITE_RHO: hipLaunchKernelGGL(k_pure_vle_rho, grid, block, 0, s, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry); break;
+            case VleKernel::ORDERED: hipLaunchKernelGGL(k_pure_vle_ordered, grid, block, 0, s, params, temp, n, p_sat, status, iters, retry, order); break;
+            case VleKernel::FP64:
+                if (int ef = launch_pure_vle_full(params, temp, n, p_sat, rho_eq, rho_vl, status, iters, retry, s)) return ef;
+        }
+        hipLaunchKernelGGL(k_pure_vle_fallback, dim3(FALLBACK_GRID), dim3(64), 0, s, params, temp, p_sat, rho_eq, rho_vl, status,
+                           iters, retry, n);
+        if (int e = launched(main == VleKernel::ORDERED ? "k_pure_vle_ordered launch" : "k_pure_vle launch")) return e;
+    }
+    if (stages & VLE_STAGE_RETRY) return launch_pure_vle_retry(params, temp, p_sat, rho_eq, rho_vl, status, iters, retry, n, s);
     return 0;
 }
 
 int pcs_pure_vle(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                  double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, VleEntry::VLE, params, temp, n, p_sat, rho_eq, rho_vl, status, iters,
+                           workspace, stream);
 }
 
 int pcs_pure_vle_fp64(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                       double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream,
-                           false, true);
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, VleEntry::FP64, params, temp, n, p_sat, rho_eq, rho_vl, status, iters,
+                           workspace, stream);
 }
 
 int pcs_pure_vapor_pressure(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_vl,
                             uint8_t* status, void* workspace, void* stream) {
-    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, params, temp, n, p_sat, nullptr, rho_vl, status, nullptr, workspace, stream,
-                           true);
+    return pure_vle_stages(VLE_STAGE_FAST | VLE_STAGE_RETRY, VleEntry::VAPOR_PRESSURE, params, temp, n, p_sat, nullptr, rho_vl, status,
+                           nullptr, workspace, stream);
 }
 
 int pcs_pure_vle_fast(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                       double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    return pure_vle_stages(VLE_STAGE_FAST, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
+    return pure_vle_stages(VLE_STAGE_FAST, VleEntry::VLE, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
 }
 
 int pcs_pure_row_order(const double* params, const double* temp, int64_t n, int32_t* order_out, void* stream) {
@@ -636,18 +364,13 @@ int pcs_pure_vle_fast_ordered(const double* params, const double* temp, int64_t 
                               uint8_t* status, int32_t* iters, void* workspace, const int32_t* order, void* stream) {
     if (int e = enter(n, params && temp && status && workspace && order, "pcs_pure_vle_fast_ordered: null required pointer"); e != GO_ON) return e;
     if (rho_eq || rho_vl) return fail_msg("pcs_pure_vle_fast_ordered", "pressure-only form: rho_eq and rho_vl must be null");
-    int32_t* retry = static_cast<int32_t*>(workspace);
-    hipStream_t s = as_stream(stream);
-    if (int ez = zero_ints(retry, 1, s)) return ez;
-    hipLaunchKernelGGL(k_pure_vle_ordered, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, params, temp, n, p_sat, status, iters, retry, order);
-    hipLaunchKernelGGL(k_pure_vle_fallback, dim3(FALLBACK_GRID), dim3(64), 0, s, params, temp, p_sat, nullptr, nullptr, status, iters,
-                       retry, n);
-    return launched("k_pure_vle_ordered launch");
+    return pure_vle_stages(VLE_STAGE_FAST, VleEntry::ORDERED, params, temp, n, p_sat, nullptr, nullptr, status, iters, workspace, stream,
+                           order);
 }
 
 int pcs_pure_vle_retry(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                        double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, void* stream) {
-    return pure_vle_stages(VLE_STAGE_RETRY, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
+    return pure_vle_stages(VLE_STAGE_RETRY, VleEntry::VLE, params, temp, n, p_sat, rho_eq, rho_vl, status, iters, workspace, stream);
 }
 
 int pcs_pure_liquid_density(const double* params, const double* temp, const double* pressure, int64_t n,
@@ -717,4 +440,3 @@ int pcs_pure_jacobian_vjp(int which, const double* params, const double* temp, c
 }
 
 }  // extern "C"
-#endif  // part 1

@@ -1,6 +1,6 @@
 // Staging of a workgroup's [n,8] parameter rows through LDS: the one definition of the pure-component kernels' workgroup
-// size, padded row and cooperative load (pure_kernels.hip, pure_critical.hip, pure_boiling.hip, pure_enthalpy.hip).
-// 256-thread workgroups, 16-byte loads, 72-byte padded rows.  The pure VLE kernels (pure_vle_rows, pure_kernels.hip) keep a
+// size, padded row and cooperative load (pure_kernels.hip, pure_fp64.hip, pure_critical.hip, pure_boiling.hip, pure_enthalpy.hip).
+// 256-thread workgroups, 16-byte loads, 72-byte padded rows.  The pure VLE kernels (pure_vle_rows.hpp) keep a
 // written-out copy of the load for their schedule's sake.
 #pragma once
 #include <hip/hip_runtime.h>

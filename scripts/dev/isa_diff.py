@@ -25,9 +25,13 @@ def unit_commands(tree, out_dir):
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
     cmds = []
-    for src, obj, extra in b.SOURCES:
-        flags = (b.FLAGS + (b.RELAXED if src in b.RELAXED_SOURCES else []) + (b.REASSOC if "-DPCS_PURE_PART=1" in extra else [])
-                 + (b.GUARDED if src in b.GUARDED_SOURCES else []) + extra)
+    for entry in b.SOURCES:
+        src, obj, extra = entry[:3]
+        if hasattr(b, "unit_flags"):
+            flags = b.unit_flags(entry)
+        else:  # a tree from before unit_flags: its build() composed the flags like this
+            flags = (b.FLAGS + (b.RELAXED if src in b.RELAXED_SOURCES else []) + (b.REASSOC if "-DPCS_PURE_PART=1" in extra else [])
+                     + (b.GUARDED if src in b.GUARDED_SOURCES else []) + extra)
         label = obj[:-2]
         cmds.append((label, ["hipcc"] + flags + ["--cuda-device-only", "-S", "-o", os.path.join(out_dir, label + ".s"),
                              os.path.join(b.CSRC, src)]))
