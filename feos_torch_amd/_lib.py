@@ -48,6 +48,7 @@ SIGNATURES = {
     "pcs_mix_bubble_dew": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_mix_bubble_dew_temperature": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_mix_density": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcs_mix_henry": (_int, [_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_mix_jacobian": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "pcs_mix_point_jacobian": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcs_gc_table_doubles": (_i64, [_int]),

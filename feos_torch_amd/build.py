@@ -67,7 +67,10 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_CONST_TABLES"], [RELAX
            ("mix_density.hip", "mix_density.o", [], [GUARDED]),
            # liquid / vapour densities of gc rows at (T, p, x): guarded like gc_kernels.hip (the evaluation is pcs_gc_derivatives'
            # along the composition line, the root is mix_density.hpp's), csrc/gc_density.hip
-           ("gc_density.hip", "gc_density.o", [], [GUARDED])]
+           ("gc_density.hip", "gc_density.o", [], [GUARDED]),
+           # Henry's law constants: strict IEEE like pure_enthalpy.hip, whose saturated-state solve the kernel runs on the solvent
+           # row before its one evaluation of the binary model, csrc/mix_henry.hpp
+           ("mix_henry.hip", "mix_henry.o", [], [])]
 # the units of a group, for reading only (no flag is chosen through them); GUARDED includes the stability analysis (NaN / inf outcomes)
 RELAXED_SOURCES = {src for src, _, _, groups in SOURCES if RELAXED in groups}
 GUARDED_SOURCES = {src for src, _, _, groups in SOURCES if GUARDED in groups}

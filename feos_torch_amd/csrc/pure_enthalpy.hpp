@@ -64,13 +64,15 @@ PCS_DEV double enthalpy_reduced(const double* q, double T, double rl, double rv)
     return (s_l - s_v) + log(rl / rv);
 }
 
-// Returns 0 (solved) or 1.  Wave-uniform call.
-PCS_DEV int enthalpy_of_vaporization(const double* par, double T_in, EnthalpyResult& out) {
-    out.dh = out.rho_v = out.rho_l = 0.0;
-    bool fail = !crit_params_ok(par) || !is_finite_bits(T_in) || !(T_in > 0.0);
-    double q[8];
+// The saturated state the enthalpy is taken at (`solve` and the polish of `form` in the header), shared with the Henry constant
+// (mix_henry.hpp).  `bad`: the caller's own reasons to fail the row.  Returns fail; a failed lane idles through the wave-uniform
+// loops on harmless values (row_or_idle) and its outputs are not to be used.  q: the row the solve ran on, T: its temperature,
+// (rl, rv): the polished densities, p_star: the equal-area reduced pressure at them -- that of the last polish step with its
+// second-order term (vle_step), or the solve's where no polish step was taken.  Wave-uniform call.
+PCS_DEV bool saturated_state(const double* par, double T_in, bool bad, double q[8], double& T, double& rl, double& rv, double& p_star) {
+    bool fail = bad || !crit_params_ok(par) || !is_finite_bits(T_in) || !(T_in > 0.0);
     row_or_idle(q, par, fail);
-    const double T = fail ? 150.0 : T_in;
+    T = fail ? 150.0 : T_in;
     VleResult r;
     r.rho_v = r.rho_l = r.p_star = 0.0;
     int st = vle_fast<false>(q, T, r, TOL_L_RHO, TOL_V_RHO);
@@ -78,7 +80,9 @@ PCS_DEV int enthalpy_of_vaporization(const double* par, double T_in, EnthalpyRes
     pure_coef<double>(c, q, T, false);
     if (st == ST_RETRY) st = vle_robust(c, r, TOL_L_RHO);
     if (st != ST_OK) fail = true;
-    double rl = fail ? 0.4 / c.ceta : r.rho_l, rv = fail ? 1e-3 * rl : r.rho_v;
+    rl = fail ? 0.4 / c.ceta : r.rho_l;
+    rv = fail ? 1e-3 * rl : r.rho_v;
+    p_star = r.p_star;
     bool conv = fail;
     for (int k = 0; k < ENTH_POLISH_IT; k++) {
         if (!conv) {
@@ -89,12 +93,21 @@ PCS_DEV int enthalpy_of_vaporization(const double* par, double T_in, EnthalpyRes
                 conv = (fabs(s.dl) <= ENTH_TOL_POLISH * rl) && (fabs(s.dv) <= ENTH_TOL_POLISH * rv);
                 rl = ln;
                 rv = vn;
+                p_star = s.p_corr;
             } else {
                 conv = true;  // not a Newton step to trust: the densities of the solve stand
             }
         }
         if (__ballot(!conv) == 0ull) break;
     }
+    return fail;
+}
+
+// Returns 0 (solved) or 1.  Wave-uniform call.
+PCS_DEV int enthalpy_of_vaporization(const double* par, double T_in, EnthalpyResult& out) {
+    out.dh = out.rho_v = out.rho_l = 0.0;
+    double q[8], T, rl, rv, p_star;
+    const bool fail = saturated_state(par, T_in, false, q, T, rl, rv, p_star);
     const double dh = (ENTH_UNIT * T) * enthalpy_reduced(q, T, rl, rv);
     if (fail || !is_finite_bits(dh) || !(dh > 0.0)) return 1;
     out.dh = dh;

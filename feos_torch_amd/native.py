@@ -547,6 +547,24 @@ def mix_density(params, kij, temperature, pressure, molefracs, phase):
     return {"rho": rho, "dpdrho": dpdrho, "status": status.view(torch.bool), "iters": iters}
 
 
+def mix_henry(params, kij, temperature, solute):
+    """Henry's law constant of component `solute` (0 or 1) at infinite dilution in the other, pure and saturated, component at
+    T [K] (pcs_mix_henry).  -> dict(h [n] Pa, rho_vl [n,2] A^-3 and p_sat [n] Pa of the pure solvent, dlnh_drho [n] A^3 =
+    d ln H / d rho_L, status bool); outputs of failed rows are 0."""
+    if solute not in (0, 1):
+        raise ValueError("solute must be 0 or 1 (component index)")
+    device = _device_of(params)
+    params = _prep(params, device, (2, 8))
+    kij = _prep(kij, device, (2,))
+    temperature = _prep(temperature, device)
+    n = temperature.shape[0]
+    _same_rows(n, parameters=params, kij=kij)
+    h, rho_vl, p_sat, dlnh_drho = _news(device, n, (n, 2), n, n)
+    status = _new(device, n, dtype=torch.uint8)
+    _call(device, "pcs_mix_henry", int(solute), params, kij, temperature, n, h, rho_vl, p_sat, dlnh_drho, status)
+    return {"h": h, "rho_vl": rho_vl, "p_sat": p_sat, "dlnh_drho": dlnh_drho, "status": status.view(torch.bool)}
+
+
 def mix_stability(params, kij, temperature, density):
     """Tangent-plane stability analysis of binary feed states (include/pcsaft_hip.h, pcs_mix_stability) at partial densities
     density [n,2] (A^-3).  -> dict(tpd [n], rho_trial [n,2], status uint8 [n]: 0 stable, 1 unstable, 2 locally unstable,

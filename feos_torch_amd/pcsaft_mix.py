@@ -152,6 +152,57 @@ class _MixDensity(torch.autograd.Function):
         return (None, *_shell.scatter(ctx.comp, packed, None, _MixDensity.COLUMNS, ctx.needs, ctx.in_devices))
 
 
+class _MixHenry(torch.autograd.Function):
+    """H [n_ok, Pa], nans [n], plan = Henry's law constant of component `solute` at infinite dilution in the other, pure and
+    saturated, component (the solvent v) in one kernel (csrc/mix_henry.hip), compacted like _BubbleDew.  H = rho_L k_B T
+    exp(mu_s(T, rho_v = rho_L, rho_s = 0)), so with gH = g H the gradient to parameters, kij and T is
+        explicit part: ONE pcs_mix_derivatives_vjp call at (rho_L, 0) with g_mu = gH on the solute's column, G[:, :19];
+        response of rho_L(theta_v, T): ONE pcs_pure_jacobian_vjp call (selector 2, the total derivative of the saturated
+            liquid density in kmol/m3) on the solvent's row with gout = gH (1/rho_L + d mu_s/d rho_v) RHO_UNIT, added to the
+            solvent's 8 columns and to T -- the weight is the forward kernel's dlnh_drho, so the two calls are independent;
+        and gH / T.
+    No gradient flows to rho_s."""
+
+    RHO_UNIT = 1e3 * (6.02214076e23 * (1e-10 * 1e-10 * 1e-10))  # kmol/m3 -> A^-3 (csrc/pcsaft_consts.hpp)
+
+    @staticmethod
+    def forward(ctx, solute, parameters, kij, temperature):
+        dev = native._device_of(parameters)
+        par = native._prep(parameters, dev, (2, 8))
+        k = native._prep(kij, dev, (2,))
+        T = native._prep(temperature, dev)
+        r = native.mix_henry(par, k, T, solute)
+        comp = native.Compaction(r["status"])
+        h = comp.gather(r["h"])
+        ctx.needs = list(ctx.needs_input_grad[1:4])
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs):
+            ctx.save_for_backward(comp.gather(par), comp.gather(k), comp.gather(T), comp.gather(r["rho_vl"]), h,
+                                  comp.gather(r["dlnh_drho"]))
+            ctx.comp = comp
+            ctx.solute = solute
+        ctx.in_devices = (parameters.device, kij.device, temperature.device)
+        return (*_shell.finish(ctx, parameters.device, [h], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        if g is None:
+            return (None,) * 4
+        par, k, T, rho_vl, h, dlnh = ctx.saved_tensors
+        s, v = ctx.solute, 1 - ctx.solute
+        gh = g.to(T.device) * h
+        zero = torch.zeros_like(gh)
+        rho2 = torch.stack((zero, rho_vl[:, 1]) if s == 0 else (rho_vl[:, 1], zero), dim=1)
+        g_mu = torch.stack((gh, zero) if s == 0 else (zero, gh), dim=1)
+        packed = native.mix_derivatives_vjp(par, k, T, rho2, g_mu=g_mu)[:, :19].contiguous()
+        g_par, g_T, _ = native.pure_jacobian_vjp("equilibrium_liquid_density", par[:, v, :], T, None, rho_vl,
+                                                 gh * dlnh * _MixHenry.RHO_UNIT, need=(True, True, False))
+        packed[:, 8 * v:8 * v + 8] += g_par
+        packed[:, 18] += g_T + gh / T
+        return (None, *_shell.scatter(ctx.comp, packed, None, _COLUMNS, ctx.needs, ctx.in_devices))
+
+
 class _MixDerivatives(torch.autograd.Function):
     """(a, p, mu, v) = derivatives(parameters[n,2,8], kij[n,2], temperature[n], density[n,2]) with gradients to all four
     inputs (feos_torch/pcsaft_mix.py:31-154, :395-420 are torch graphs in the reference)."""
@@ -332,6 +383,26 @@ class PcSaftMix(_shell.Reducible):
         vapour branch ends below p (and for the invalid inputs of liquid_density).  Tuple order, reduction and gradients as
         for liquid_density."""
         return self._density(1, temperature, pressure, vapor_molefracs)
+
+    def henrys_law_constant(self, temperature, solute=1):
+        """(H [Pa], nans): Henry's law constant of component `solute` (index 0 or 1) at infinite dilution in the other
+        component, the solvent, at T [K]:  H = lim_{x_s -> 0} f_s / x_s = rho_L k_B T exp(mu_s^res), with rho_L the saturated
+        liquid density of the PURE solvent and mu_s^res the solute's residual chemical potential at (rho_solvent = rho_L,
+        rho_solute = 0) -- the fugacity-based constant; the K-factor form y p / x differs from it by the solute's
+        vapour-phase fugacity coefficient.  One kernel (include/pcsaft_hip.h, pcs_mix_henry).  This class's (value, nans)
+        order; values for the solved rows only; the model is reduced like bubble_point does.  A row fails where a parameter
+        of either component or kij is invalid, T is not finite and positive, the solvent has no vapour-liquid equilibrium at
+        T (T >= T_c of the solvent), or H is not finite and positive; a supercritical solute is an ordinary row.
+        Differentiable w.r.t. parameters, kij and temperature (the solvent's saturated density responds to its parameters
+        and T: pcs_mix_derivatives_vjp plus pcs_pure_jacobian_vjp, no kernel of its own).  Not part of the reference's class."""
+        if self.ncomp != 2:
+            raise Exception("henrys_law_constant is implemented for binary mixtures")
+        if isinstance(solute, bool) or solute not in (0, 1):
+            raise ValueError("solute must be 0 or 1 (component index)")
+        temperature = temperature if isinstance(temperature, torch.Tensor) else torch.as_tensor(temperature, dtype=torch.float64)
+        h, nans, comp = _MixHenry.apply(int(solute), self._par, self.kij, temperature)
+        self._reduce(comp)
+        return h, nans
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of binary feed states at T [K] and partial densities density [N,2] (A^-3) -- the model's

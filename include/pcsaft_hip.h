@@ -344,6 +344,37 @@ int pcs_mix_density(int phase, const double* params, const double* kij, const do
                     void* workspace, void* stream);
 
 /*
+ * Henry's law constant of a solute at infinite dilution in a pure, saturated solvent (ABI 117), one kernel
+ * (csrc/mix_henry.hpp).  With s the solute (component index `solute`), v the other component (the solvent), rho_L the
+ * saturated liquid density of the PURE solvent at T and mu_s = da/drho_s the residual chemical potential of the binary
+ * model at the partial densities rho_v = rho_L, rho_s = 0 (the mu of pcs_mix_derivatives there):
+ *     H = lim_{x_s -> 0} f_s / x_s = rho_L k_B T exp(mu_s) = rho_L [A^-3] T (k_B / A^3) exp(mu_s)        [Pa]
+ * the fugacity-based (IUPAC) constant.  The K-factor form y p / x differs from it by the solute's vapour-phase fugacity
+ * coefficient and is not computed; rho_vl and p_sat are handed out for a caller who composes it with pcs_mix_derivatives.
+ * The solvent's saturated state is that of pcs_pure_enthalpy_of_vaporization (the all-fp64 VLE solve, densities polished by
+ * exact coupled Newton updates until the relative step is below 1e-10, at most three): H is not stationary in the density.
+ * The reference has no counterpart.
+ *   solute                0 or 1: the component at infinite dilution; anything else is an error return
+ *   params    [n,2,8] in   (16-byte aligned)
+ *   kij       [n,2]   in   (16-byte aligned) as for pcs_mix_bubble_dew
+ *   temp      [n]     in   K
+ *   h         [n]     out  Pa
+ *   rho_vl    [n,2]   out  A^-3, (rho_V, rho_L) of the pure solvent at T                              (optional)
+ *   p_sat     [n]     out  Pa, the pure solvent's vapour pressure (equal-area pressure at rho_vl)      (optional)
+ *   dlnh_drho [n]     out  A^3, d ln H / d rho_L = 1 / rho_L + d mu_s / d rho_v at (rho_L, 0)          (optional)
+ *   status    [n]     out  uint8, 0 = solved, 1 = failed; outputs of a failed row are 0.  A row fails when a parameter of
+ *                          EITHER component is non-finite or m, sigma, eps <= 0 or kappa, eps_ab, na, nb < 0, kij is
+ *                          non-finite, T is non-finite or <= 0, the solvent has no equilibrium at T (every T >= T_c of the
+ *                          solvent), or H is non-finite or <= 0.  A supercritical solute is an ordinary row.
+ * A row's result does not depend on the rows it shares a wave with.  Backward pass, no kernel of its own, with upstream g
+ * on H: G = pcs_mix_derivatives_vjp at (rho_L, 0) with g_mu = g H on the solute's column and no other weight gives the
+ * explicit part G[:, :19]; the response of rho_L is pcs_pure_jacobian_vjp (selector 2, value in kmol/m3) on the solvent's
+ * parameter row with gout = g H dlnh_drho x (1e3 N_A 1e-30), added to the solvent's 8 columns and to T; and g H / T.
+ */
+int pcs_mix_henry(int solute, const double* params, const double* kij, const double* temp, int64_t n, double* h,
+                  double* rho_vl, double* p_sat, double* dlnh_drho, uint8_t* status, void* stream);
+
+/*
  * PcSaftMix.derivatives (feos_torch/pcsaft_mix.py:395-420) at given partial densities rho [n,2]:
  * a [n], p [n] (reduced), residual chemical potentials mu [n,2], partial molar volumes v [n,2].
  * Any output may be NULL.

@@ -32,6 +32,9 @@ with HIP events on the launch stream, inputs resident in HBM.
             bubble pressure (liquid) / 0.5 x the dew pressure (vapour) of the same process's bubble_point / dew_point (1e5 Pa
             where those fail); pcs_gc_derivatives and the bubble / dew solve alongside, the same kernel without the class
             order, forward + backward through the model class, failed rows and the histogram of evaluations per row
+  henry: PcSaftMix.henrys_law_constant kernel (pcs_mix_henry) on mix_batch(1e6), either solute; next to it what the same number
+            costs without it -- pcs_pure_vle_fp64 on the solvent rows plus pcs_mix_derivatives at (rho_L, 0) with the gathers
+            between them, and each of the two alone --, forward + backward through the model class, failed rows
 Prints one JSON object per config."""
 import json
 import os
@@ -371,3 +374,36 @@ if "gc_density" in which:
                           "ms_without_class_order": ms_plain, "same_bits_without_class_order": bool(same), "ms_gc_derivatives": ms_deriv,
                           "ms_bubble_dew_point": ms_point, "ms_forward_backward": ms_fb, "failed": int(r["status"].sum()),
                           "failed_point": int(rp["status"].sum()), "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
+if "henry" in which:
+    # one row per lane in batch order.  What a user pays today for the same number: the all-fp64 pure VLE solve on the solvent
+    # rows plus one state evaluation at (rho_L, 0), with the gathers between them (the solvent's parameter row, rho_L into [n,2])
+    from feos_torch_amd import PcSaftMix
+    n = 1_000_000
+    P, K, T, _, _ = mix_batch(n)
+    a = [d(v) for v in (P, K, T)]
+    for solute in (0, 1):
+        v = 1 - solute
+        ms, r = timed(lambda: native.mix_henry(*a, solute), reps=5)
+
+        def unfused():
+            vle = native.pure_vle(a[0][:, v, :].contiguous(), a[2], all_fp64=True)
+            rho2 = torch.zeros((n, 2), dtype=torch.float64, device="cuda")
+            rho2[:, v] = torch.where(vle["status"], torch.full_like(a[2], 5e-3), vle["rho_vl"][:, 1])
+            return vle, native.mix_derivatives(a[0], a[1], a[2], rho2)
+        ms_unfused, (vle, _) = timed(unfused, reps=5)
+        Pv = a[0][:, v, :].contiguous()
+        ms_vle, _ = timed(lambda: native.pure_vle(Pv, a[2], all_fp64=True), reps=5)
+        rho2 = torch.zeros((n, 2), dtype=torch.float64, device="cuda")
+        rho2[:, v] = torch.where(r["status"], torch.full_like(a[2], 5e-3), r["rho_vl"][:, 1])
+        ms_deriv, _ = timed(lambda: native.mix_derivatives(a[0], a[1], a[2], rho2), reps=5)
+
+        def fwd_bwd():
+            leaves = [x.clone().requires_grad_(True) for x in a]
+            h, _ = PcSaftMix(leaves[0], leaves[1]).henrys_law_constant(leaves[2], solute=solute)
+            h.log().sum().backward()
+            return leaves[0].grad
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        print(json.dumps({"config": f"PcSaftMix henrys_law_constant solute={solute} batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_vle_fp64_plus_mix_derivatives_with_gathers": ms_unfused, "ms_pure_vle_fp64": ms_vle,
+                          "ms_mix_derivatives": ms_deriv, "ms_forward_backward": ms_fb, "failed": int(r["status"].sum()),
+                          "failed_pure_vle_fp64": int(vle["status"].sum())}))
