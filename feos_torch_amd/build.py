@@ -68,6 +68,9 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_CONST_TABLES"], [RELAX
            # liquid / vapour densities of gc rows at (T, p, x): guarded like gc_kernels.hip (the evaluation is pcs_gc_derivatives'
            # along the composition line, the root is mix_density.hpp's), csrc/gc_density.hip
            ("gc_density.hip", "gc_density.o", [], [GUARDED]),
+           # saturation pressure / saturated densities of one molecule of a gc row as a pure fluid: guarded like gc_density.hip
+           # (the same evaluation along the lines x = 1 / x = 0; the solve is csrc/gc_saturation.hpp), csrc/gc_saturation.hip
+           ("gc_saturation.hip", "gc_saturation.o", [], [GUARDED]),
            # Henry's law constants: strict IEEE like pure_enthalpy.hip, whose saturated-state solve the kernel runs on the solvent
            # row before its one evaluation of the binary model, csrc/mix_henry.hpp
            ("mix_henry.hip", "mix_henry.o", [], [])]

@@ -387,6 +387,90 @@ class _GcDensity(torch.autograd.Function):
         return (None, None, gk, gphi, gT, gp, gx, *gs)
 
 
+class _GcSaturation(torch.autograd.Function):
+    """value [n_ok], nans [n], plan = saturation pressure [Pa] (which 0) or saturated liquid density [kmol/m3] (which 1) of
+    molecule `component` of every row taken as a pure fluid, in one kernel (csrc/gc_saturation.hip), compacted like _GcDensity.
+
+    Backward: no kernel of its own, two pcs_gc_derivatives_vjp calls -- at the vapour (rho_V, 0) and at the liquid (rho_L, 0),
+    component 1: (0, rho) -- that add into one grad_seg; their jac9 blocks are added too (the k_ab, phi and T chains are linear
+    in them, and agg does not depend on the density).  Notation: a the reduced residual Helmholtz energy density, p the reduced
+    pressure (the vjp's own a and p), @ a partial derivative at fixed densities, dv = 1/rho_V - 1/rho_L, theta any parameter.
+      p_sat.  The reduced equal-area pressure p* = -(a_V/rho_V - a_L/rho_L + ln(rho_V/rho_L)) / dv is stationary in both
+        densities at the solution (d p*/d rho_k = (p* - p_k) / (rho_k^2 dv) = 0), so
+            dp*/dtheta = -(@a_V/@theta / rho_V - @a_L/@theta / rho_L) / dv.
+        With p_sat = p* T k_B 1e30 and an upstream gradient g: w = g T k_B 1e30,
+            g_a = -w / (rho_V dv) on the vapour call,   g_a = +w / (rho_L dv) on the liquid call,
+        and d p_sat/dT = g k_B 1e30 p* (= g p_sat / T) + the summed jac9[:, 6].
+      rho_L.  It is defined by p_L(rho_L, theta) = p*(theta), so with p'_L = dp/drho along the line at the liquid root
+            d rho_L/dtheta = (dp*/dtheta - @p_L/@theta) / p'_L:
+        the weights of p_sat with w = g c / p'_L (c = A^-3 -> kmol/m3), and g_p = -g c / p'_L on the liquid call as well.  Both
+        p* and p_L are reduced pressures of one T: the temperature column is the summed jac9[:, 6], no p/T term appears.
+    The segment vectors are the columns of grad_seg; k_ab and phi are the pressure's own chains on the summed jac9[:, :6]
+    (_kab_gradient, _phi_gradient), as in _GcDensity.backward.  The class order is used by the backward calls only when no
+    row was dropped."""
+
+    @staticmethod
+    def forward(ctx, which, component, model, kab, phi, temperature, *segment_parameters):
+        dev, S = model.device, model.S
+        table = _device_table(model.seg, kab, dev)
+        ph = native._prep(phi, dev, (2,))
+        T = native._prep(temperature, dev)
+        order = _class_order(model, table)
+        r = native.gc_pure_vle(table, S, model.rows, ph, T, component, order=order, want=("p_sat", "rho_vl", "dpdrho_vl"))
+        comp = native.Compaction(r["status"])
+        value = comp.gather(r["p_sat"]) if which == 0 else comp.gather(r["rho_vl"])[:, 1] * _GcDensity.C
+        ctx.needs = list(ctx.needs_input_grad[3:6])  # k_ab, phi, temperature
+        ctx.seg_needs = list(ctx.needs_input_grad[6:])
+        ctx.set_materialize_grads(False)
+        ctx.comp = None
+        if any(ctx.needs) or any(ctx.seg_needs):
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": comp.gather(T),
+                    "rho_vl": comp.gather(r["rho_vl"]), "aux": value if which == 0 else comp.gather(r["dpdrho_vl"])[:, 1].contiguous()}
+            if comp.all_ok:  # the class order belongs to the uncompacted rows
+                keep["order"] = order
+            ctx.kept = tuple(keep)
+            ctx.save_for_backward(*keep.values())
+            ctx.comp = comp
+        ctx.S, ctx.which, ctx.component = S, which, component
+        ctx.seg_devs = [q.device for q in segment_parameters]
+        ctx.devs = tuple(t.device for t in (kab, phi, temperature))
+        return (*_shell.finish(ctx, phi.device, [value], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        nseg = len(ctx.seg_needs)
+        comp, S = ctx.comp, ctx.S
+        if g is None or comp is None:
+            return (None,) * (6 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T, aux = kept["table"], kept["rows"], kept["ph"], kept["T"], kept["aux"]
+        rv, rl = kept["rho_vl"][:, 0], kept["rho_vl"][:, 1]
+        g = g.to(table.device)
+        dv = 1.0 / rv - 1.0 / rl
+        if ctx.which == 0:
+            w, g_p = g * T / _GcDensity.P_RED, None
+        else:
+            w = g * _GcDensity.C / aux  # aux: dp/drho at the liquid root
+            g_p = -w
+        zero = torch.zeros_like(rv)
+        at = lambda rho: torch.stack((rho, zero) if ctx.component == 0 else (zero, rho), dim=1)
+        gseg, jac_v, agg = native.gc_derivatives_vjp(table, S, rows, ph, T, at(rv), g_a=-w / (rv * dv), order=kept.get("order"))
+        gseg, jac_l, _ = native.gc_derivatives_vjp(table, S, rows, ph, T, at(rl), g_a=w / (rl * dv), g_p=g_p, order=kept.get("order"),
+                                                   grad_seg=gseg)
+        jac9 = jac_v + jac_l
+        gk = gphi = gT = None
+        if ctx.needs[0]:
+            gk = _kab_gradient(table, S, rows, ph, T, jac9[:, 1], jac9[:, 4]).to(ctx.devs[0])
+        if ctx.needs[1]:
+            gphi = comp.expand(_phi_gradient(jac9, agg, ph)).to(ctx.devs[1])
+        if ctx.needs[2]:
+            dT = jac9[:, 6] + g * aux / T if ctx.which == 0 else jac9[:, 6].contiguous()  # aux: p_sat [Pa]
+            gT = comp.expand(dT).view(comp.n).to(ctx.devs[2])
+        gs = [gseg[:, k].to(dev) if need else None for k, (dev, need) in enumerate(zip(ctx.seg_devs, ctx.seg_needs))]
+        return (None, None, None, gk, gphi, gT, *gs)
+
+
 class GcPcSaftMix(_shell.Reducible):
     def __init__(self, segment_identifier, parameter, segment_lists, bond_lists, binary_segment_records, phi=None):
         """Arguments as the reference (feos_torch/gc_pcsaft.py:14-22): segment identifiers [S], the
@@ -506,6 +590,33 @@ class GcPcSaftMix(_shell.Reducible):
         branch ends below p (and for the invalid inputs of liquid_density).  Tuple order, reduction and gradients as for
         liquid_density."""
         return self._density(1, temperature, pressure, vapor_molefracs)
+
+    def _saturation(self, which, temperature, component):
+        if isinstance(component, bool) or not isinstance(component, (int, np.integer)) or component not in (0, 1):
+            raise ValueError("component must be 0 or 1 (the index of the molecule of each row that is taken as a pure fluid)")
+        temperature = temperature if isinstance(temperature, torch.Tensor) else torch.as_tensor(temperature, dtype=torch.float64)
+        value, nans, comp = _GcSaturation.apply(which, int(component), self, self.kab, self.phi, temperature, *self._segment_parameters)
+        self._reduce(comp)
+        return value, nans
+
+    def vapor_pressure(self, temperature, component=0):
+        """(p_sat [Pa], nans): saturation pressure at T [K] of molecule `component` (index 0 or 1, the convention of
+        PcSaftMix.henrys_law_constant(solute=...)) of every row taken as a pure fluid -- the contract of
+        PcSaftPure.vapor_pressure on the gc model, in one kernel (include/pcsaft_hip.h, pcs_gc_pure_vle).  Values for the solved
+        rows only; the model is reduced like liquid_density does.  A row fails where T is not finite or T <= 0, phi is not
+        finite, or the pure fluid has no vapour-liquid equilibrium at T (every T at or above its critical temperature); a
+        failed row never carries the trivial solution rho_V = rho_L or an "equilibrium" between two dense states.
+        Differentiable w.r.t. the eight segment parameter vectors, k_ab, phi and temperature (two pcs_gc_derivatives_vjp calls,
+        see _GcSaturation).  The model applies k_ab between segments of unlike molecules only (feos_torch/gc_pcsaft.py:177-194),
+        so the k_ab gradient of a pure fluid is exactly zero, as is that of the other molecule's phi.  Any other `component`,
+        including True, None or 0.5, raises ValueError.  Not part of the reference's class."""
+        return self._saturation(0, temperature, component)
+
+    def equilibrium_liquid_density(self, temperature, component=0):
+        """(rho_L [kmol/m3], nans): saturated liquid density at T [K] of molecule `component` of every row taken as a pure
+        fluid, the contract of PcSaftPure.equilibrium_liquid_density on the gc model; kernel, failure rules, reduction and
+        gradients as for vapor_pressure."""
+        return self._saturation(1, temperature, component)
 
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction

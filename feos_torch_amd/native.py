@@ -789,6 +789,34 @@ def gc_density(table, S, rows, phi, temperature, pressure, molefracs, phase, ord
     return {"rho": rho, "dpdrho": dpdrho, "status": status.view(torch.bool), "iters": iters}
 
 
+def gc_pure_vle(table, S, rows, phi, temperature, component=0, order=None, want=("p_sat", "rho_vl", "dpdrho_vl", "iters")):
+    """Vapour-liquid equilibrium of molecule `component` (0 or 1) of every gc row as a pure fluid at T [K] (pcs_gc_pure_vle).
+    table / rows / order as for gc_bubble_dew.  -> dict(p_sat [n] Pa, rho_vl [n,2] (rho_V, rho_L) A^-3, dpdrho_vl [n,2] reduced
+    dp/drho at the two roots, status bool, iters int32 evaluations, -1 for failed rows); outputs of failed rows are 0.  want:
+    the optional outputs to compute (the others are passed as NULL and left out of the dict)."""
+    if isinstance(component, bool) or component not in (0, 1):
+        raise ValueError("component must be 0 or 1 (molecule index)")
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature = _prep(temperature, device)
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi)
+    _check_order(order, n, device)
+    out = {"p_sat": _new(device, n) if "p_sat" in want else None,
+           "rho_vl": _new(device, (n, 2)) if "rho_vl" in want else None,
+           "dpdrho_vl": _new(device, (n, 2)) if "dpdrho_vl" in want else None}
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if "iters" in want else None
+    _call(device, "pcs_gc_pure_vle", int(component), table, int(S), rows, phi, temperature, n, out["p_sat"], out["rho_vl"],
+          out["dpdrho_vl"], status, iters, order)
+    out = {k: v for k, v in out.items() if v is not None}
+    out["status"] = status.view(torch.bool)
+    if iters is not None:
+        out["iters"] = iters
+    return out
+
+
 def gc_stability(table, S, rows, phi, temperature, density, order=None):
     """mix_stability for gc rows (pcs_gc_stability); order: optional class order of the rows (gc_class_order), schedule
     only.  -> dict(tpd, rho_trial, status)."""
@@ -909,8 +937,10 @@ def mix_derivatives_vjp(params, kij, temperature, density, g_a=None, g_p=None, g
     return grad
 
 
-def gc_derivatives_vjp(table, S, rows, phi, temperature, density, g_a=None, g_p=None, g_mu=None, g_v=None, order=None):
-    """Backward of GcPcSaftMix.derivatives: -> (grad_seg [S,8], jac9 [n,9] = dL/d(6 aggregates, T, rho_0, rho_1), agg [n,6])."""
+def gc_derivatives_vjp(table, S, rows, phi, temperature, density, g_a=None, g_p=None, g_mu=None, g_v=None, order=None,
+                       grad_seg=None):
+    """Backward of GcPcSaftMix.derivatives: -> (grad_seg [S,8], jac9 [n,9] = dL/d(6 aggregates, T, rho_0, rho_1), agg [n,6]).
+    grad_seg: an earlier call's [S,8] sum on the device of the table, which this call adds to and returns (None: a new one)."""
     device = table.device
     phi = _prep(phi, device, (2,))
     temperature, density = _prep(temperature, device), _prep(density, device, (2,))
@@ -918,7 +948,12 @@ def gc_derivatives_vjp(table, S, rows, phi, temperature, density, g_a=None, g_p=
     n = temperature.shape[0]
     _check_gc(table, S, rows, n)
     _same_rows(n, phi=phi, density=density, g_a=g_a, g_p=g_p, g_mu=g_mu, g_v=g_v)
-    gseg = torch.zeros((int(S), 8), dtype=_F64, device=device)
+    if grad_seg is None:
+        gseg = torch.zeros((int(S), 8), dtype=_F64, device=device)
+    else:
+        gseg = grad_seg
+        if gseg.dtype != _F64 or tuple(gseg.shape) != (int(S), 8) or gseg.device != device or not gseg.is_contiguous():
+            raise ValueError(f"grad_seg must be a contiguous float64 tensor [{int(S)}, 8] on the device of the table")
     jac9, agg = _news(device, (n, 9), (n, 6))
     _call(device, "pcs_gc_derivatives_vjp", table, int(S), rows, phi, temperature, density, n, g_a, g_p, g_mu, g_v, gseg,
           jac9, agg, _order_or_none(order, n))

@@ -550,6 +550,43 @@ int pcs_gc_density(int phase, const double* table, int S, const uint8_t* rows, c
                    const double* pressure, const double* x, int64_t n, double* rho, double* dpdrho, uint8_t* status,
                    int32_t* iters, const int32_t* order, void* stream);
 
+/*
+ * Vapour-liquid equilibrium of ONE molecule of a gc-PC-SAFT row taken as a pure fluid (ABI 118): saturation pressure and
+ * saturated densities at given T, one kernel (csrc/gc_saturation.hip on pure_line_vle of csrc/gc_saturation.hpp).  The pure
+ * fluid is the composition line x = 1 (component 0) or x = 0 (component 1) of the row's model -- k_ab acts between segments
+ * of unlike molecules only, so it does not enter --, evaluated as pcs_gc_density evaluates it: p = rho - a + rho a',
+ * dp/drho = 1 + rho a''.  Solve: the algorithm of the pure-component robust pass (csrc/pure_solver.hpp, vle_robust) --
+ * zero-pressure liquid from eta = 0.5 with the vapour at the liquid's fugacity, else both spinodals and branch solves at the
+ * mean of their pressures; coupled Newton on the equal-area pressure p* = -(f_V - f_L)/(v_V - v_L), f = a/rho + ln rho, with
+ * backtracking onto the stable branches -- then further Newton updates until both relative steps are below 1e-10 (at most
+ * three) and one closing evaluation at the final densities.  The reference has no counterpart.
+ *   component             0 or 1: the molecule of each row that is taken as a pure fluid; anything else is an error return
+ *   table, S, rows, phi   in   as for pcs_gc_bubble_dew (rows 16-byte aligned)
+ *   temp      [n]    in   K
+ *   p_sat     [n]    out  Pa: p* T k_B 1e30 with the second-order corrected p* of the closing step       (optional)
+ *   rho_vl    [n,2]  out  (rho_V, rho_L) in A^-3                                                         (optional)
+ *   dpdrho_vl [n,2]  out  the reduced dp/drho at the two roots (> 0): what the backward pass of rho_L needs (optional)
+ *   status    [n]    out  uint8, 1 = failed; outputs of such rows are 0.  A row fails AT ONCE when T is non-finite or <= 0 or
+ *                         phi is non-finite; otherwise where the pure fluid has no vapour-liquid equilibrium at T (every T at
+ *                         or above its critical temperature: no van der Waals loop, or a non-positive vapour-spinodal
+ *                         pressure), where the iteration does not converge within its caps, or where the converged state is
+ *                         not accepted: the trivial solution rho_V = rho_L, a pressure that is not 0 < p* <= 1.0001 rho_V (an
+ *                         "equilibrium" between two dense states on a second van der Waals loop), or a mechanically unstable
+ *                         state at one of the eight halvings of rho_V (the vapour root must lie on the branch from zero
+ *                         density).  A failed row never carries any of these.
+ *   iters     [n]    out  int32 model evaluations used, -1 for failed rows (optional, diagnostics)
+ *   order     [n]    in   optional class order of the rows as for pcs_gc_bubble_dew (NULL: bucketed by class inside each
+ *                         workgroup); only the schedule changes, results are identical.  One row per lane, no work queue.
+ * A row's result does not depend on the rows it shares a wave with, on n or on order.  Backward pass: two
+ * pcs_gc_derivatives_vjp calls accumulating into one grad_seg, at (rho_V, 0) and (rho_L, 0) (component 1: (0, rho)).  With
+ * dv = 1/rho_V - 1/rho_L, w = g T k_B 1e30 for an upstream gradient g of p_sat: g_a = -w / (rho_V dv) on the vapour call,
+ * g_a = +w / (rho_L dv) on the liquid call (p* is stationary in both densities); d p_sat/dT = g p_sat / T + sum of jac9[:, 6].
+ * For rho_L (p_L(rho_L, theta) = p*(theta)): the same with w = g / dpdrho_L, plus g_p = -g / dpdrho_L on the liquid call.
+ */
+int pcs_gc_pure_vle(int component, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
+                    int64_t n, double* p_sat, double* rho_vl, double* dpdrho_vl, uint8_t* status, int32_t* iters,
+                    const int32_t* order, void* stream);
+
 /* GcPcSaftMix.derivatives (feos_torch/gc_pcsaft.py:443-468): a, p, mu [n,2], v [n,2] at rho [n,2]. */
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream);

@@ -35,6 +35,10 @@ with HIP events on the launch stream, inputs resident in HBM.
   henry: PcSaftMix.henrys_law_constant kernel (pcs_mix_henry) on mix_batch(1e6), either solute; next to it what the same number
             costs without it -- pcs_pure_vle_fp64 on the solvent rows plus pcs_mix_derivatives at (rho_L, 0) with the gathers
             between them, and each of the two alone --, forward + backward through the model class, failed rows
+  gc_saturation: GcPcSaftMix.vapor_pressure / equilibrium_liquid_density kernel (pcs_gc_pure_vle) on gc_batch(1e6) in class order,
+            either component, at 0.7 x the critical-temperature estimate of gc_batch for that molecule; next to it the liquid
+            plus the vapour pcs_gc_density call at the resulting p_sat on the same rows (x = 1 / x = 0), forward + backward
+            through the model class, failed rows and the histogram of evaluations per row
 Prints one JSON object per config."""
 import json
 import os
@@ -407,3 +411,48 @@ if "henry" in which:
                           "ms_vle_fp64_plus_mix_derivatives_with_gathers": ms_unfused, "ms_pure_vle_fp64": ms_vle,
                           "ms_mix_derivatives": ms_deriv, "ms_forward_backward": ms_fb, "failed": int(r["status"].sum()),
                           "failed_pure_vle_fp64": int(vle["status"].sum())}))
+if "gc_saturation" in which:
+    # one row per lane in class order, no work queue: a wave pays its slowest row, and the solve is the robust one of the pure
+    # path (no fp32 pre-solve).  The neighbours on the same rows: the two density roots at the p_sat this kernel returns
+    from feos_torch_amd import GcPcSaftMix
+    n = 1_000_000
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    par = tuple(torch.tensor([v[k] for _, v in table], dtype=torch.float64, requires_grad=True) for k in range(8))
+    phi_leaf = d(b["phi"]).requires_grad_(True)
+    model = GcPcSaftMix(ident, par, b["segment_lists"], b["bond_lists"], b["kab_list"], phi_leaf)
+    tab, S, rows = model._table(), model.S, model.rows
+    phi = phi_leaf.detach()
+    order = native.gc_class_order(tab, S, rows)
+    seg_par = dict(table)
+    tc_of = {}
+
+    def tc_estimate(segs):  # the estimate gc_batch takes its temperatures from, per molecule (the lists are shared objects)
+        if id(segs) not in tc_of:
+            m = np.array([seg_par[s][0] for s in segs]); e = np.array([seg_par[s][2] for s in segs])
+            tc_of[id(segs)] = (m * e).sum() / m.sum() * 1.28 * m.sum() ** 0.45
+        return tc_of[id(segs)]
+    for component in (0, 1):
+        T = d(0.7 * np.array([tc_estimate(row[component]) for row in b["segment_lists"]]))
+        ms, r = timed(lambda: native.gc_pure_vle(tab, S, rows, phi, T, component, order=order), reps=5)
+        ms_p, _ = timed(lambda: native.gc_pure_vle(tab, S, rows, phi, T, component, order=order, want=("p_sat",)), reps=5)
+        ok = ~r["status"]
+        p = torch.where(ok, r["p_sat"], torch.full_like(T, 1e5)).contiguous()
+        x = torch.full_like(T, 1.0 - component)
+        ms_liq, rl = timed(lambda: native.gc_density(tab, S, rows, phi, T, p, x, 0, order=order), reps=5)
+        ms_vap, rv = timed(lambda: native.gc_density(tab, S, rows, phi, T, p, x, 1, order=order), reps=5)
+
+        def fwd_bwd(method):
+            model.rows, model.phi, model._order = rows, phi_leaf, order  # the call reduces the model: start from all rows
+            leaf = T.clone().requires_grad_(True)
+            value, _ = getattr(model, method)(leaf, component=component)
+            value.sum().backward()
+            return leaf.grad
+        ms_fb_p, _ = timed(lambda: fwd_bwd("vapor_pressure"), reps=3)
+        ms_fb_rho, _ = timed(lambda: fwd_bwd("equilibrium_liquid_density"), reps=3)
+        print(json.dumps({"config": f"GcPcSaftMix vapor_pressure component={component} batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_p_sat_only": ms_p, "ms_gc_density_liquid_at_p_sat": ms_liq, "ms_gc_density_vapour_at_p_sat": ms_vap,
+                          "over_two_density_calls": ms / (ms_liq + ms_vap), "ms_forward_backward_vapor_pressure": ms_fb_p,
+                          "ms_forward_backward_equilibrium_liquid_density": ms_fb_rho, "failed": int(r["status"].sum()),
+                          "failed_density_liquid": int((rl["status"] & ok).sum()), "failed_density_vapour": int((rv["status"] & ok).sum()),
+                          "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
