@@ -31,6 +31,7 @@ SIGNATURES = {
     "pcs_expand_rows": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "pcs_pure_vle_fast": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_row_order": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "pcs_pure_order_key": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "pcs_pure_vle_fast_ordered": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_vle_fp64": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_pure_vle_retry": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -508,13 +508,26 @@ PCS_DEV EvalF pure_eval_start_f32(const PureCoefF& c) {
 
 PCS_DEV bool finitef(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+// What the pre-solve did on a row, for the row order (pcs_pure_row_order sorts on it) and its probe; the solving kernels
+// pass no PreSignature and none of this is computed there.  Margins are quotients value / threshold of the pre-solve's own
+// stop decisions: <= 1 means the decision fell on the cheap side.
+constexpr float PRE_MARGIN_OPEN = 1e30f;  // the decision was never reached on its cheap side (restart, failure)
+enum : int { PRE_SIG_REEVAL = 1, PRE_SIG_FULL_V = 2 };
+struct PreSignature {
+    int n_liq, n_cpl, code;  // liquid-root evaluations (0..12), coupled iterations (0..8), failure code (0: none)
+    int flags;               // PRE_SIG_REEVAL / PRE_SIG_FULL_V: a full liquid / vapour evaluation in a coupled iteration >= 2
+    float m_liq;             // liquid root, second evaluation: |scaled Newton step| / (tolerance rho); 0 when the first one ended it
+    float m_l, m_v;          // second coupled iteration: max(pl / PCS_F32_PREDICT_TOL_L, sl / 1e-2), max(pv / PCS_F32_PREDICT_TOL_V, sv / 1e-2); 0: not run
+};
+
 struct LiquidRootF {
     float rl;
     bool ok, done, dense;
     int first;  // iteration at which the current start density is evaluated
+    float m2;   // signature only: step of the second evaluation over its tolerance (0: done at the first, huge: no Newton step there)
 };
 // One iteration of liquid_root_f32 from the evaluation `e` at s.rl.  AT_START: s.rl is the start density (iteration 0).
-template <bool AT_START>
+template <bool AT_START, bool SIG = false>
 PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float tol_dense, int it, const EvalF& e, LiquidRootF& s) {
     const float res = e.p - p_spec;
     // rung of the ladder eta = 0.58, 0.66, 0.74 above this start (a start within 0.005 below a rung takes the one after it, so
@@ -545,7 +558,14 @@ PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float
         if (!(den > 0.0f)) step = 2.0f * s.rl;  // -> rn < 0 -> this lane takes the fp64 initialiser
         float rn = s.rl - step;
         if (!(rn > 0.0f)) { s.ok = false; s.done = true; }
-        else { s.done = fabsf(step) <= (s.dense ? tol_dense : tol) * s.rl; s.rl = rn; }
+        else {
+            s.done = fabsf(step) <= (s.dense ? tol_dense : tol) * s.rl;
+            if constexpr (SIG) {
+                if (AT_START) s.m2 = s.done ? 0.0f : PRE_MARGIN_OPEN;
+                else if (it == 1) s.m2 = fabsf(step) * __builtin_amdgcn_rcpf((s.dense ? tol_dense : tol) * s.rl);
+            }
+            s.rl = rn;
+        }
     }
 }
 // fp32 liquid root of p(rho) = p_spec from eta = 0.5.  Newton on (p - p_spec)(1-eta)^4 = 0 (same root):
@@ -557,9 +577,11 @@ PCS_DEV void liquid_root_step(const PureCoefF& f, float p_spec, float tol, float
 // (monotone from there) and the tighter `tol_dense`.
 // Wave-uniform loop; returns false when the lane must use the fp64 initialiser.  Iteration 0 is peeled: every lane is at
 // eta0 there and takes pure_eval_start_f32.
+template <bool SIG = false>
 PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float tol_dense, int cap, float& rl,
-                             int& n_eval) {
+                             int& n_eval, float* m2 = nullptr) {
     LiquidRootF s;
+    if constexpr (SIG) s.m2 = PRE_MARGIN_OPEN;
     s.ok = finitef(f.da) && finitef(f.kd2) && finitef(f.ceta) && f.ceta > 0.0f && finitef(p_spec);
     s.rl = start_rho_f32(f);
     s.done = !s.ok;
@@ -569,14 +591,14 @@ PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float 
     // dense-side restarts share their iterations with other lanes' Newton evaluations and stay generic.
     if (cap > 0) {
         if (!s.done) {
-            liquid_root_step<true>(f, p_spec, tol, tol_dense, 0, pure_eval_start_f32(f), s);
+            liquid_root_step<true, SIG>(f, p_spec, tol, tol_dense, 0, pure_eval_start_f32(f), s);
             n_eval++;
         }
         if (__ballot(!s.done) != 0ull) {
 #pragma unroll 1
             for (int it = 1; it < cap; it++) {
                 if (!s.done) {
-                    liquid_root_step<false>(f, p_spec, tol, tol_dense, it, pure_eval_f32(f, s.rl), s);
+                    liquid_root_step<false, SIG>(f, p_spec, tol, tol_dense, it, pure_eval_f32(f, s.rl), s);
                     n_eval++;
                 }
                 if (__ballot(!s.done) == 0ull) break;
@@ -584,6 +606,7 @@ PCS_DEV bool liquid_root_f32(const PureCoefF& f, float p_spec, float tol, float 
         }
     }
     rl = s.rl;
+    if constexpr (SIG) *m2 = s.m2;
     return s.ok && s.done;
 }
 
@@ -606,14 +629,18 @@ struct PreState {
     bool lean_v;          // the lane's next vapour evaluation may be the one without the second derivative
     int it, n_liq, code;  // coupled iterations done; diagnostics
     bool ok, done;
+    float m_liq, m_l, m_v;  // signature only (PreSignature)
+    int flags;
 };
 
+template <bool SIG = false>
 PCS_DEV void presolve_begin(const PureCoefF& f, PreState& s) {
     s.n_liq = 0; s.it = 0; s.code = 0;
+    if constexpr (SIG) { s.m_liq = PRE_MARGIN_OPEN; s.m_l = 0.0f; s.m_v = 0.0f; s.flags = 0; }
     s.dpv = 1.0f; s.sl_prev = 1.0f; s.sv_prev = 1.0f;
     s.pv = 0.0f; s.dv_taken = 0.0f; s.ev = 0.0f; s.sec_prev = 0.0f; s.d_prev = 0.0f; s.lean_v = false;
     // zero-pressure liquid, handed over to the coupled iteration at a loose step
-    bool ok = liquid_root_f32(f, 0.0f, PCS_F32_LIQ_TOL, 1e-2f, 12, s.rl, s.n_liq);
+    bool ok = liquid_root_f32<SIG>(f, 0.0f, PCS_F32_LIQ_TOL, 1e-2f, 12, s.rl, s.n_liq, &s.m_liq);
     const float rl = s.rl;
     s.l = pure_eval_f32(f, rl);
     float rv = rl * f_exp(s.l.mu);
@@ -667,6 +694,7 @@ PCS_DEV bool carry_slope(float p0, float p1, float drho, float s, float mu, floa
     return true;
 }
 
+template <bool SIG = false>
 PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
     float rl = s.rl, rv = s.rv;
     EvalF l = s.l;
@@ -676,6 +704,9 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
     float pv_last = s.pv, dv_taken = s.dv_taken, ev = s.ev, sec_prev = s.sec_prev, d_prev = s.d_prev;
     bool lean_v = s.lean_v;
     int n_cpl = s.it;
+    float m_l = 0.0f, m_v = 0.0f;  // signature only
+    int flags = 0;
+    if constexpr (SIG) { m_l = s.m_l; m_v = s.m_v; flags = s.flags; }
     // `it` below only bounds the loop, the lane's own count n_cpl decides what the first-iteration rule of the stop
     // criterion sees
     for (int it = 0; it < it_end; it++) {
@@ -699,6 +730,7 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
         if (__ballot(full) != 0ull) {
             if (full) {
                 v = pure_eval_f32(f, rv);
+                if constexpr (SIG) { if (n_cpl >= 1) flags |= PRE_SIG_FULL_V; }
                 dpv_last = v.dp;
                 ev = 0.0f;
                 d_prev = 0.0f;
@@ -726,6 +758,10 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
                 float pl = sl * sl * fminf(sl * __builtin_amdgcn_rcpf(sl_prev * sl_prev), PCS_F32_PREDICT_CMAX);
                 float pv = sv * fmaf(sv, fminf(sv * __builtin_amdgcn_rcpf(sv_prev * sv_prev), PCS_F32_PREDICT_CMAX), ev);
                 done = ((sl <= 2e-6f) && (sv <= 3e-5f)) || (n_cpl > 0 && sl < 1e-2f && sv < 1e-2f && pl <= PCS_F32_PREDICT_TOL_L && pv <= PCS_F32_PREDICT_TOL_V);
+                if constexpr (SIG) if (n_cpl == 1) {
+                    m_l = fmaxf(pl * (1.0f / PCS_F32_PREDICT_TOL_L), sl * 1e2f);
+                    m_v = fmaxf(pv * (1.0f / PCS_F32_PREDICT_TOL_V), sv * 1e2f);
+                }
                 sl_prev = sl; sv_prev = sv;
                 dl_taken = rln - rl;
                 dv_taken = rvn - rv;
@@ -752,7 +788,10 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
                 l.p = fmaf(l.dp, dl_taken, l.p);
             }
             if (__ballot(reeval) != 0ull) {
-                if (reeval) l = pure_eval_f32(f, rl);
+                if (reeval) {
+                    l = pure_eval_f32(f, rl);
+                    if constexpr (SIG) { if (n_cpl >= 2) flags |= PRE_SIG_REEVAL; }
+                }
             }
         }
         if (__ballot(!done && n_cpl < it_end) == 0ull) break;
@@ -760,18 +799,20 @@ PCS_DEV void presolve_coupled(const PureCoefF& f, PreState& s, int it_end) {
     s.rl = rl; s.rv = rv; s.l = l; s.dpv = dpv_last; s.sl_prev = sl_prev; s.sv_prev = sv_prev;
     s.pv = pv_last; s.dv_taken = dv_taken; s.ev = ev; s.sec_prev = sec_prev; s.d_prev = d_prev; s.lean_v = lean_v;
     s.it = n_cpl; s.ok = ok; s.done = done;
+    if constexpr (SIG) { s.m_l = m_l; s.m_v = m_v; s.flags = flags; }
 }
 
+template <bool SIG = false>
 PCS_DEV bool vle_presolve_f32(const PureCoefF& f, double& rl_out, double& rv_out, float& dpl_out, float& dpv_out,
-                              int* diag = nullptr) {
+                              PreSignature* sig = nullptr) {
     PreState s;
-    presolve_begin(f, s);
-    presolve_coupled(f, s, 8);
+    presolve_begin<SIG>(f, s);
+    presolve_coupled<SIG>(f, s, 8);
     rl_out = (double)s.rl;
     rv_out = (double)s.rv;
     dpl_out = s.l.dp;
     dpv_out = s.dpv;
-    if (diag) *diag = s.n_liq | (s.it << 8) | (s.code << 16);  // diagnostics builds only
+    if constexpr (SIG) *sig = PreSignature{s.n_liq, s.it, s.code, s.flags, s.m_liq, s.m_l, s.m_v};  // the order kernels only
     return s.ok;
 }
 

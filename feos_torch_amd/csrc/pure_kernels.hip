@@ -33,7 +33,7 @@ __global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_rho(const dou
 }
 
 // the pressure-only kernel on rows in a reusable tile-local order: p_sat, status and the list as k_pure_vle<true, false>
-// (the list's entries in another sequence), no counting sort, class- and tau-uniform waves from a domain of ORDER_TILE rows
+// (the list's entries in another sequence), no counting sort, waves of one class and like pre-solve work from a domain of ORDER_TILE rows
 __global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_ordered(const double* __restrict__ params,
                                                     const double* __restrict__ temp, int64_t n,
                                                     double* __restrict__ p_sat, uint8_t* __restrict__ status,
@@ -42,66 +42,76 @@ __global__ __launch_bounds__(BLOCK, K1_WAVES_LITE) void k_pure_vle_ordered(const
     pure_vle_rows<true, false, false, true>(params, temp, n, p_sat, nullptr, nullptr, status, iters, retry, order);
 }
 
-// The order k_pure_vle_ordered consumes: one workgroup per tile of ORDER_TILE rows, counting sort in LDS by
-// (class in k1_bucket's Gray order, tau bin); order_out[tile] is a permutation of the tile's row indices, the sequence inside
-// a bucket is whatever the LDS atomics give.  tau = T / (1.28 m^0.45 eps) in fp32, the reduced temperature the fp32
-// pre-solve's evaluation and iteration counts follow; ORDER_TAU_BINS equal bins over the range of tau in the tile itself
-// (a first pass takes its minimum and maximum in LDS), so a data set with a narrow or shifted temperature range keeps all its
-// bins; tau is held to [0, ORDER_TAU_CAP] (NaN counts as 0) so that an invalid row cannot stretch the range without bound.
-// Tile size and bin count from the host-permuted ceiling measurement (scripts/dev/tile_order_ab.py):
-// 16384 rows, 8 bins.
+// The order k_pure_vle_ordered consumes, in two kernels.  k_pure_order_key: one row per lane in batch order, the fp32
+// pre-solve itself (pure_coef_f32 + vle_presolve_f32 with its PreSignature), and into order_out[row] the row's key
+// class * ORDER_SUB + order_subkey -- a function of the row alone.  k_pure_row_order: one workgroup per tile of ORDER_TILE
+// rows, the tile's keys from order_out into LDS, counting sort there, the tile's permutation written over them;
+// order_out[tile] is a permutation of the tile's row indices, the sequence inside a bucket is whatever the LDS atomics give.
+// Tile size from the host-permuted ceiling measurement (scripts/dev/tile_order_ab.py): 16384 rows.
 constexpr int ORDER_TILE = 16384;
-constexpr int ORDER_TAU_BINS = 8;
-constexpr int ORDER_BINS = K1_BINS * ORDER_TAU_BINS;
-constexpr float ORDER_TAU_CAP = 2.0f;
+constexpr int ORDER_SUB = 64;  // sub-keys per class
+constexpr int ORDER_BINS = K1_BINS * ORDER_SUB;
 static_assert(ORDER_TILE % BLOCK == 0 && ORDER_BINS <= BLOCK && ORDER_BINS <= 256, "one key byte per row, one lane per bin");
-__device__ __forceinline__ float order_tau(const double* row, double T) {
-    const float tau = (float)T / (1.28f * (float)row[2] * __powf((float)row[0], 0.45f));
-    return fminf(fmaxf(tau, 0.0f), ORDER_TAU_CAP);  // fmaxf(NaN, 0) = 0
+// Sub-key of a row whose pre-solve succeeded, from the margins of its two stop decisions and not from the counts: rows near a
+// threshold sit next to each other, so a row that changes sides when the parameters move spoils the waves around a bin edge
+// only (an order on the bare counts is the fastest on the parameters it was built from and slower than the tau order on
+// moved ones: profiles/cost_order_step0.json).  With c = max(m_l, m_v), q = m_liq, both held to [2^-5, 2^5]:
+//   major = floor(log2(c c)) + 8 in 0..15   (half-octave bins of the second coupled iteration's margin over [2^-4, 2^4])
+//   minor = (floor(log2 q) + 4) >> 1 in 0..3 (two-octave bins of the liquid root's margin), running backwards in odd majors
+// floor(log2 x) is the exponent field of x: no logarithm, and a host can repeat the key bit for bit.
+constexpr int ORDER_MAJOR = 16, ORDER_MINOR = 4;
+static_assert(ORDER_MAJOR * ORDER_MINOR == ORDER_SUB, "sub-key = major * ORDER_MINOR + minor");
+__device__ __forceinline__ int order_exponent(float x) { return (int)((__float_as_uint(x) >> 23) & 0xffu) - 127; }
+__device__ __forceinline__ int order_subkey(const PreSignature& g) {
+    const float c = fminf(fmaxf(fmaxf(g.m_l, g.m_v), 0.03125f), 32.0f), q = fminf(fmaxf(g.m_liq, 0.03125f), 32.0f);
+    const int major = min(max(order_exponent(c * c) + 8, 0), ORDER_MAJOR - 1);
+    const int minor = min(max((order_exponent(q) + 4) >> 1, 0), ORDER_MINOR - 1);
+    return major * ORDER_MINOR + ((major & 1) ? ORDER_MINOR - 1 - minor : minor);
 }
-__global__ __launch_bounds__(BLOCK) void k_pure_row_order(const double* __restrict__ params, const double* __restrict__ temp,
-                                                          int64_t n, int32_t* __restrict__ order_out) {
+// RAW (pcs_pure_order_key): also raw[4 row ..] = n_liq | n_cpl << 8 | code << 16 | flags << 24 | usable << 31, then the bits
+// of the margins m_liq, m_l, m_v (PreSignature, pure_f32.hpp)
+template <bool RAW>
+__global__ __launch_bounds__(BLOCK) void k_pure_order_key(const double* __restrict__ params, const double* __restrict__ temp,
+                                                          int64_t n, int32_t* __restrict__ key_out, int32_t* __restrict__ raw) {
+    const LaneRow row = stage_lane_row(params, n);
+    const double T = temp[row.ii];
+    PureCoefF f;
+    pure_coef_f32(f, row.par, T);
+    double rl, rv;
+    float dpl, dpv;
+    PreSignature sig;
+    const bool warm = vle_presolve_f32<true>(f, rl, rv, dpl, dpv, &sig);  // every lane of the wave makes the call
+    if (!row.live) return;
+    bool usable = warm && is_finite_bits(T) && T > 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) usable = usable && is_finite_bits(row.par[k]) && (k > 2 || row.par[k] > 0.0);
+    key_out[row.i] = k1_bucket(row.par) * ORDER_SUB + (usable ? order_subkey(sig) : ORDER_SUB - 1);
+    if constexpr (RAW) {
+        int32_t* o = raw + 4 * row.i;
+        o[0] = (int32_t)((uint32_t)sig.n_liq | (uint32_t)sig.n_cpl << 8 | (uint32_t)sig.code << 16 | (uint32_t)sig.flags << 24 | (usable ? 0x80000000u : 0u));
+        o[1] = __float_as_int(sig.m_liq);
+        o[2] = __float_as_int(sig.m_l);
+        o[3] = __float_as_int(sig.m_v);
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_pure_row_order(int64_t n, int32_t* __restrict__ order_out) {
     __shared__ uint8_t keys[ORDER_TILE];
     __shared__ int bins[ORDER_BINS];
-    __shared__ int range[2];  // bits of the smallest / largest tau of the tile: non-negative floats order as their bits do
     const int t = threadIdx.x;
     const int64_t tile0 = (int64_t)blockIdx.x * ORDER_TILE;
     const int count = (int)min((int64_t)ORDER_TILE, n - tile0);
     if (t < ORDER_BINS) bins[t] = 0;
-    if (t == 0) {
-        range[0] = __float_as_int(ORDER_TAU_CAP);
-        range[1] = 0;
-    }
     __syncthreads();
-    {
-        float lo = ORDER_TAU_CAP, hi = 0.0f;
-        for (int j = t; j < count; j += BLOCK) {
-            const float tau = order_tau(params + 8 * (tile0 + j), temp[tile0 + j]);
-            lo = fminf(lo, tau);
-            hi = fmaxf(hi, tau);
-        }
-        atomicMin(&range[0], __float_as_int(lo));
-        atomicMax(&range[1], __float_as_int(hi));
-    }
-    __syncthreads();
-    const float tau_lo = __int_as_float(range[0]), width = __int_as_float(range[1]) - tau_lo;
-    const float per_tau = width > 0.0f ? (float)ORDER_TAU_BINS / width : 0.0f;
     for (int j = t; j < count; j += BLOCK) {
-        const double* row = params + 8 * (tile0 + j);
-        const int bin = (int)fminf((order_tau(row, temp[tile0 + j]) - tau_lo) * per_tau, (float)(ORDER_TAU_BINS - 1));
-        const int key = k1_bucket(row) * ORDER_TAU_BINS + max(bin, 0);
+        const int key = min(max(order_out[tile0 + j], 0), ORDER_BINS - 1);
         keys[j] = (uint8_t)key;
         atomicAdd(&bins[key], 1);
     }
+    __syncthreads();  // every key of the tile is in LDS: order_out[tile] may be overwritten from here on
+    int first = 0;    // lane b: where bucket b starts, its own serial sum over the buckets before it (no cheaper than a scan)
+    for (int b = 0; b < t && b < ORDER_BINS; b++) first += bins[b];
     __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-        for (int b = 0; b < ORDER_BINS; b++) {
-            const int c = bins[b];
-            bins[b] = acc;
-            acc += c;
-        }
-    }
+    if (t < ORDER_BINS) bins[t] = first;
     __syncthreads();
     for (int j = t; j < count; j += BLOCK) order_out[tile0 + atomicAdd(&bins[keys[j]], 1)] = (int32_t)(tile0 + j);
 }
@@ -265,14 +275,14 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives_vjp(const double* __
 
 extern "C" {
 
-int pcs_abi_version(void) { return 118; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+int pcs_abi_version(void) { return 119; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
                                             // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp);
                                             // 107: pcs_pure_start_probe; 108: pcs_pure_boiling_temperature, Jacobian selector 3;
                                             // 109: pcs_pure_enthalpy_of_vaporization(_vjp); 110: pcs_mix_bubble_dew_temperature;
                                             // 111: pcs_mix_point_jacobian; 112: pcs_gc_bubble_dew_temperature;
                                             // 113: pcs_gc_point_jacobian, pcs_gc_point_segment_gradient; 114: pcs_mix_density;
                                             // 115: pcs_gc_density; 116: pcs_pure_row_order, pcs_pure_vle_fast_ordered;
-                                            // 117: pcs_mix_henry; 118: pcs_gc_pure_vle
+                                            // 117: pcs_mix_henry; 118: pcs_gc_pure_vle; 119: pcs_pure_order_key
 
 const char* pcs_last_error(void) { return g_err; }
 
@@ -356,8 +366,15 @@ int pcs_pure_vle_fast(const double* params, const double* temp, int64_t n, doubl
 
 int pcs_pure_row_order(const double* params, const double* temp, int64_t n, int32_t* order_out, void* stream) {
     if (int e = enter(n, params && temp && order_out, "pcs_pure_row_order: null required pointer"); e != GO_ON) return e;
-    hipLaunchKernelGGL(k_pure_row_order, dim3(grid_for(n, ORDER_TILE)), dim3(BLOCK), 0, as_stream(stream), params, temp, n, order_out);
+    hipLaunchKernelGGL(k_pure_order_key<false>, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), params, temp, n, order_out, nullptr);
+    hipLaunchKernelGGL(k_pure_row_order, dim3(grid_for(n, ORDER_TILE)), dim3(BLOCK), 0, as_stream(stream), n, order_out);
     return launched("k_pure_row_order launch");
+}
+
+int pcs_pure_order_key(const double* params, const double* temp, int64_t n, int32_t* key_out, int32_t* raw_out, void* stream) {
+    if (int e = enter(n, params && temp && key_out && raw_out, "pcs_pure_order_key: null required pointer"); e != GO_ON) return e;
+    hipLaunchKernelGGL(k_pure_order_key<true>, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), params, temp, n, key_out, raw_out);
+    return launched("k_pure_order_key launch");
 }
 
 // stage 1 of the pressure-only solve on rows in the order of pcs_pure_row_order: reset, k_pure_vle_ordered, fallback

@@ -392,17 +392,20 @@ class PureVlePlan:
     current HIP stream (no allocation, no host synchronisation), so steps can be timed with
     HIP events.
 
-    A pressure-only plan (the default) keeps a tile-local row order (``pcs_pure_row_order``: model class, then a bin of the
-    reduced temperature) and solves through ``pcs_pure_vle_fast_ordered``: waves of one class and similar iteration counts.
+    A pressure-only plan (the default) keeps a tile-local row order (``pcs_pure_row_order``: model class, then bins of how close
+    the fp32 pre-solve, which the order kernel runs once on every row, came to needing a third coupled iteration and a third
+    liquid-root evaluation) and solves through ``pcs_pure_vle_fast_ordered``: waves of one class and like iteration counts.
     The order is built by the first ``run`` / ``run_fast`` with usable inputs and kept: it is a scheduling hint, results
     do not depend on it, and in a parameter fit the classes and temperatures of the data points stay while the parameters
     move.  ``reorder`` rebuilds it; ``ordered=False`` gives the plain entries.
 
-    The kept order belongs to the ROWS of the first call.  Moved parameters cost it little (measured x1.16 instead of x1.18
-    against the plain path after a +-5 % move), but a plan reused for a DIFFERENT batch of the same n (minibatches, streaming)
-    runs with an order that carries no information, and the ordered kernel does not sort by itself: that measured 13 %
-    SLOWER than the plain path.  Results are right either way.  Such callers pass ``ordered=False``, or call ``reorder`` for
-    every new batch (one kernel, a quarter of a solve)."""
+    The kept order belongs to the ROWS of the first call.  Moved parameters cost it part of its gain (measured x1.19 instead of
+    x1.22 against the plain path after a +-5 % move of m, sigma, epsilon), but a plan reused for a DIFFERENT batch of the same n
+    (minibatches, streaming) runs with an order that carries no information, and the ordered kernel does not sort by itself:
+    that measured 15 % SLOWER than the plain path.  Results are right either way.  Such callers pass ``ordered=False``.
+    ``reorder`` is no remedy for them: it is two kernels and costs 0.60 ms per 1e7 rows, 1.1 ordered solves (it runs the
+    pre-solve on unsorted rows), against 0.12 ms that an ordered solve saves, so it pays only from the fifth launch on the
+    same rows -- a fit, or a batch that comes back."""
 
     def __init__(self, n, device, want_rho_eq=False, want_rho_vl=False, all_fp64=False, ordered=True):
         self.all_fp64 = bool(all_fp64)
@@ -427,7 +430,7 @@ class PureVlePlan:
                    for x in (params, temperature)) and tuple(params.shape) == (self.n, 8) and tuple(temperature.shape) == (self.n,)
 
     def reorder(self, params, temperature):
-        """Rebuild the row order from these parameters and temperatures (one kernel on the current stream)."""
+        """Rebuild the row order from these parameters and temperatures (two kernels on the current stream)."""
         if not self.ordered:
             raise ValueError("this plan keeps no row order")
         if not self._usable(params, temperature):

@@ -75,8 +75,11 @@ int pcs_pure_vle_retry(const double* params, const double* temp, int64_t n, doub
  * A reusable row order for the pressure-only fast stage (ABI 116).
  *   pcs_pure_row_order         writes order_out (int32[n]): the batch is cut into tiles of 16384 consecutive rows (the last one
  *                              may be short) and the entries of a tile are a permutation of that tile's row indices, ordered
- *                              by model class (none, polar, polar + associating, associating) and, inside a class, by a bin
- *                              of the reduced temperature T / (1.28 m^0.45 eps).  One kernel, no host synchronisation.
+ *                              by model class (none, polar, polar + associating, associating) and, inside a class, by the
+ *                              sub-key of pcs_pure_order_key: the fp32 pre-solve is run on every row and the rows are binned
+ *                              by how close it came to a third coupled iteration and a third liquid-root evaluation.  Two
+ *                              kernels (order_out is the first one's scratch), no memset, no host synchronisation: capturable.
+ *                              It costs about as much as one solve: for rows that are solved many times.
  *   pcs_pure_vle_fast_ordered  pcs_pure_vle_fast in its pressure-only form (rho_eq and rho_vl must be null) with lane t of
  *                              the kernel solving row order[t]: waves then hold rows of one class and similar iteration counts.
  * The order is a scheduling hint: rows are independent, so p_sat, status and the set of listed rows are bit for bit those
@@ -88,6 +91,17 @@ int pcs_pure_row_order(const double* params, const double* temp, int64_t n, int3
 int pcs_pure_vle_fast_ordered(const double* params, const double* temp, int64_t n, double* p_sat, double* rho_eq,
                               double* rho_vl, uint8_t* status, int32_t* iters, void* workspace, const int32_t* order,
                               void* stream);
+
+/*
+ * Probe of the row order's key (ABI 119; tests and scripts/dev/k1_wave_stats.py): what pcs_pure_row_order sorts on, per row.
+ *   key_out [n] int32    class * 64 + sub-key (class: none 0, polar 1, polar + associating 2, associating 3)
+ *   raw_out [n,4] int32  what the fp32 pre-solve did on the row: liquid-root evaluations | coupled iterations << 8 |
+ *                        failure code << 16 | flags << 24 (1: a full liquid, 2: a full vapour evaluation in a coupled
+ *                        iteration >= 2) | usable << 31 (finite, positive inputs and a pre-solve that succeeded), then the
+ *                        bits of three fp32 margins value / threshold of its stop decisions: the liquid root's second step,
+ *                        the liquid and the vapour side of the second coupled iteration.
+ */
+int pcs_pure_order_key(const double* params, const double* temp, int64_t n, int32_t* key_out, int32_t* raw_out, void* stream);
 
 /*
  * pcs_pure_vle with the all-fp64 main kernel (fp64 value / first / second derivative in every Newton iteration after the

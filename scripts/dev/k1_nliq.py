@@ -2,8 +2,10 @@
 #   python scripts/dev/k1_nliq.py [--out FILE.json] <variant> ...      (scratch/ab/lib_<variant>.so)
 # Needs a diagnostic build (a copy of csrc/, see README.md) that writes to `iters`
 #   n_liq | dense << 6 | coupled iterations << 8 | code << 16 | fp64-finish iterations << 24
-# (vle_fast_lite hands `diag` of vle_presolve_f32 on; liquid_root_f32 sets bit 6 of n_eval for a lane that restarted on the
-# dense side).  Waves are the kernel's: the 256 rows of a workgroup in the order of k1_bucket, 64 to a wave.
+# (vle_fast_lite calls vle_presolve_f32<true> with a PreSignature and packs its n_liq, n_cpl and code into the word it adds to
+# res.iters; liquid_root_f32 sets bit 6 of n_eval for a lane that restarted on the dense side).  The counts alone, without the
+# dense flag and the finish iterations, come from pcs_pure_order_key of the product library: k1_wave_stats.py.
+# Waves are the kernel's: the 256 rows of a workgroup in the order of k1_bucket, 64 to a wave.
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); os.chdir(ROOT)
 import numpy as np, torch
