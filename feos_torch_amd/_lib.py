@@ -57,6 +57,7 @@ SIGNATURES = {
     "pcs_gc_bubble_dew_temperature": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_gc_density": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_gc_pure_vle": (_int, [_int, _vp, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcs_gc_henry": (_int, [_int, _vp, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcs_gc_derivatives": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pcs_gc_jacobian": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcs_gc_segment_gradient": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

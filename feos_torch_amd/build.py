@@ -73,7 +73,10 @@ SOURCES = [("pure_kernels.hip", "pure_kernels.o", ["-DPCS_CONST_TABLES"], [RELAX
            ("gc_saturation.hip", "gc_saturation.o", [], [GUARDED]),
            # Henry's law constants: strict IEEE like pure_enthalpy.hip, whose saturated-state solve the kernel runs on the solvent
            # row before its one evaluation of the binary model, csrc/mix_henry.hpp
-           ("mix_henry.hip", "mix_henry.o", [], [])]
+           ("mix_henry.hip", "mix_henry.o", [], []),
+           # gc Henry's law constants: guarded like gc_saturation.hip, whose per-lane solve runs on the solvent molecule before the
+           # kernel's one two-variable evaluation (the arithmetic of pcs_gc_derivatives), csrc/gc_henry.hpp
+           ("gc_henry.hip", "gc_henry.o", [], [GUARDED])]
 # the units of a group, for reading only (no flag is chosen through them); GUARDED includes the stability analysis (NaN / inf outcomes)
 RELAXED_SOURCES = {src for src, _, _, groups in SOURCES if RELAXED in groups}
 GUARDED_SOURCES = {src for src, _, _, groups in SOURCES if GUARDED in groups}

@@ -275,14 +275,15 @@ __global__ __launch_bounds__(BLOCK) void k_pure_derivatives_vjp(const double* __
 
 extern "C" {
 
-int pcs_abi_version(void) { return 119; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
+int pcs_abi_version(void) { return 120; }  // 103: pcs_pure_vapor_pressure, pcs_compact_* / pcs_expand_rows; 104: pcs_pure_vle_fp64;
                                             // 105: pcs_mix_stability, pcs_gc_stability; 106: pcs_pure_critical_point(_vjp);
                                             // 107: pcs_pure_start_probe; 108: pcs_pure_boiling_temperature, Jacobian selector 3;
                                             // 109: pcs_pure_enthalpy_of_vaporization(_vjp); 110: pcs_mix_bubble_dew_temperature;
                                             // 111: pcs_mix_point_jacobian; 112: pcs_gc_bubble_dew_temperature;
                                             // 113: pcs_gc_point_jacobian, pcs_gc_point_segment_gradient; 114: pcs_mix_density;
                                             // 115: pcs_gc_density; 116: pcs_pure_row_order, pcs_pure_vle_fast_ordered;
-                                            // 117: pcs_mix_henry; 118: pcs_gc_pure_vle; 119: pcs_pure_order_key
+                                            // 117: pcs_mix_henry; 118: pcs_gc_pure_vle; 119: pcs_pure_order_key;
+                                            // 120: pcs_gc_henry
 
 const char* pcs_last_error(void) { return g_err; }
 

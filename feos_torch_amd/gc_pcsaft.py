@@ -471,6 +471,83 @@ class _GcSaturation(torch.autograd.Function):
         return (None, None, None, gk, gphi, gT, *gs)
 
 
+class _GcHenry(torch.autograd.Function):
+    """H [n_ok, Pa], nans [n], plan = Henry's law constant of molecule `solute` of every row at infinite dilution in the other,
+    pure and saturated, molecule (the solvent v = 1 - solute) in one kernel (csrc/gc_henry.hip), compacted like _GcSaturation.
+    H = rho_L k_B T exp(mu_s), rho_L the solvent's saturated liquid density, mu_s the solute's residual chemical potential at
+    the partial densities rho_v = rho_L, rho_s = 0.
+
+    Backward: no kernel of its own, the two pcs_gc_derivatives_vjp calls of _GcSaturation (which 1) -- at the solvent's vapour
+    (rho_V on column v, 0) and liquid (rho_L on column v, 0) -- adding into one grad_seg, with one more weight.  For any
+    parameter theta, at fixed T,
+        d ln H/dtheta = @mu_s/@theta + dlnh_drho d rho_L/dtheta,    dlnh_drho = 1/rho_L + @mu_s/@rho_v (the kernel's output),
+    and d rho_L/dtheta = (dp*/dtheta - @p_L/@theta) / p'_L with p* stationary in both densities, as _GcSaturation derives it.
+    With gH = g H for an upstream gradient g of H, dv = 1/rho_V - 1/rho_L and w = gH dlnh_drho / p'_L:
+        vapour call: g_a = -w / (rho_V dv);      liquid call: g_a = +w / (rho_L dv), g_p = -w, g_mu[:, s] = gH.
+    T has the explicit factor of H = rho_L T k_B 1e30 exp(mu_s) on top: the summed jac9[:, 6] + gH / T.  The segment vectors are
+    the columns of grad_seg; k_ab and phi are the chains on the summed jac9[:, :6] -- unlike the pure methods both phi columns
+    and k_ab receive gradients here, through @mu_s/@theta.  The class order is used by the backward calls only when no row was
+    dropped."""
+
+    @staticmethod
+    def forward(ctx, solute, model, kab, phi, temperature, *segment_parameters):
+        dev, S = model.device, model.S
+        table = _device_table(model.seg, kab, dev)
+        ph = native._prep(phi, dev, (2,))
+        T = native._prep(temperature, dev)
+        order = _class_order(model, table)
+        r = native.gc_henry(table, S, model.rows, ph, T, solute, order=order, want=("rho_vl", "dlnh_drho", "dpdrho_l"))
+        comp = native.Compaction(r["status"])
+        h = comp.gather(r["h"])
+        ctx.needs = list(ctx.needs_input_grad[2:5])  # k_ab, phi, temperature
+        ctx.seg_needs = list(ctx.needs_input_grad[5:])
+        ctx.set_materialize_grads(False)
+        ctx.comp = None
+        if any(ctx.needs) or any(ctx.seg_needs):
+            keep = {"table": table, "rows": comp.gather(model.rows), "ph": comp.gather(ph), "T": comp.gather(T),
+                    "rho_vl": comp.gather(r["rho_vl"]), "h": h, "dlnh_drho": comp.gather(r["dlnh_drho"]),
+                    "dpdrho_l": comp.gather(r["dpdrho_l"])}
+            if comp.all_ok:  # the class order belongs to the uncompacted rows
+                keep["order"] = order
+            ctx.kept = tuple(keep)
+            ctx.save_for_backward(*keep.values())
+            ctx.comp = comp
+        ctx.S, ctx.solute = S, solute
+        ctx.seg_devs = [q.device for q in segment_parameters]
+        ctx.devs = tuple(t.device for t in (kab, phi, temperature))
+        return (*_shell.finish(ctx, phi.device, [h], r["status"]), comp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        nseg = len(ctx.seg_needs)
+        comp, S = ctx.comp, ctx.S
+        if g is None or comp is None:
+            return (None,) * (5 + nseg)
+        kept = dict(zip(ctx.kept, ctx.saved_tensors))
+        table, rows, ph, T = kept["table"], kept["rows"], kept["ph"], kept["T"]
+        rv, rl = kept["rho_vl"][:, 0], kept["rho_vl"][:, 1]
+        gh = g.to(table.device) * kept["h"]
+        dv = 1.0 / rv - 1.0 / rl
+        w = gh * kept["dlnh_drho"] / kept["dpdrho_l"]
+        zero = torch.zeros_like(rv)
+        at = lambda rho: torch.stack((zero, rho) if ctx.solute == 0 else (rho, zero), dim=1)  # rho on the solvent's column
+        g_mu = torch.stack((gh, zero) if ctx.solute == 0 else (zero, gh), dim=1)
+        gseg, jac_v, agg = native.gc_derivatives_vjp(table, S, rows, ph, T, at(rv), g_a=-w / (rv * dv), order=kept.get("order"))
+        gseg, jac_l, _ = native.gc_derivatives_vjp(table, S, rows, ph, T, at(rl), g_a=w / (rl * dv), g_p=-w, g_mu=g_mu,
+                                                   order=kept.get("order"), grad_seg=gseg)
+        jac9 = jac_v + jac_l
+        gk = gphi = gT = None
+        if ctx.needs[0]:
+            gk = _kab_gradient(table, S, rows, ph, T, jac9[:, 1], jac9[:, 4]).to(ctx.devs[0])
+        if ctx.needs[1]:
+            gphi = comp.expand(_phi_gradient(jac9, agg, ph)).to(ctx.devs[1])
+        if ctx.needs[2]:
+            gT = comp.expand(jac9[:, 6] + gh / T).view(comp.n).to(ctx.devs[2])
+        gs = [gseg[:, k].to(dev) if need else None for k, (dev, need) in enumerate(zip(ctx.seg_devs, ctx.seg_needs))]
+        return (None, None, gk, gphi, gT, *gs)
+
+
 class GcPcSaftMix(_shell.Reducible):
     def __init__(self, segment_identifier, parameter, segment_lists, bond_lists, binary_segment_records, phi=None):
         """Arguments as the reference (feos_torch/gc_pcsaft.py:14-22): segment identifiers [S], the
@@ -592,8 +669,7 @@ class GcPcSaftMix(_shell.Reducible):
         return self._density(1, temperature, pressure, vapor_molefracs)
 
     def _saturation(self, which, temperature, component):
-        if isinstance(component, bool) or not isinstance(component, (int, np.integer)) or component not in (0, 1):
-            raise ValueError("component must be 0 or 1 (the index of the molecule of each row that is taken as a pure fluid)")
+        _molecule_index(component, "component", "taken as a pure fluid")
         temperature = temperature if isinstance(temperature, torch.Tensor) else torch.as_tensor(temperature, dtype=torch.float64)
         value, nans, comp = _GcSaturation.apply(which, int(component), self, self.kab, self.phi, temperature, *self._segment_parameters)
         self._reduce(comp)
@@ -618,6 +694,25 @@ class GcPcSaftMix(_shell.Reducible):
         gradients as for vapor_pressure."""
         return self._saturation(1, temperature, component)
 
+    def henrys_law_constant(self, temperature, solute=1):
+        """(H [Pa], nans): Henry's law constant at T [K] of molecule `solute` (index 0 or 1) of every row at infinite dilution in
+        the other molecule of the row, taken as a pure, saturated liquid (the solvent v) -- the contract of
+        PcSaftMix.henrys_law_constant on the gc model: H = rho_L k_B T exp(mu_s), with rho_L the solvent's saturated liquid
+        density (that of equilibrium_liquid_density(T, component=v)) and mu_s the solute's residual chemical potential at the
+        partial densities rho_v = rho_L, rho_s = 0 (derivatives).  It is the fugacity-based constant; the K-factor form y p / x
+        is not computed.  One kernel (include/pcsaft_hip.h, pcs_gc_henry).  Values for the solved rows only; the model is
+        reduced like vapor_pressure does.  A row fails where T is not finite or T <= 0, phi is not finite, the solvent has no
+        vapour-liquid equilibrium at T (every failure of vapor_pressure), or H is not finite or <= 0; a supercritical solute is
+        an ordinary row.  Differentiable w.r.t. the eight segment parameter vectors, k_ab, phi and temperature (two
+        pcs_gc_derivatives_vjp calls, see _GcHenry); unlike the pure methods k_ab and both phi columns receive non-zero
+        gradients, which is what makes infinite-dilution data a target for fitting k_ab.  Any other `solute`, including True,
+        None or 0.5, raises ValueError.  Not part of the reference's class."""
+        _molecule_index(solute, "solute", "infinitely dilute")
+        temperature = temperature if isinstance(temperature, torch.Tensor) else torch.as_tensor(temperature, dtype=torch.float64)
+        h, nans, comp = _GcHenry.apply(int(solute), self, self.kab, self.phi, temperature, *self._segment_parameters)
+        self._reduce(comp)
+        return h, nans
+
     def stability_analysis(self, temperature, density):
         """Tangent-plane stability of the model's rows at T [K] and partial densities density [N,2] (A^-3), without reduction
         or autograd graph: (stable bool [N], tpd [N], trial_density [N,2]) as PcSaftMix.stability_analysis."""
@@ -637,6 +732,12 @@ class GcPcSaftMix(_shell.Reducible):
 
     def _compute_device(self):
         return self.device
+
+
+def _molecule_index(value, name, role):
+    """the check of `component` / `solute`: a plain integer 0 or 1 (not True, None or 0.5), before anything touches the device"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value not in (0, 1):
+        raise ValueError(f"{name} must be 0 or 1 (the index of the molecule of each row that is {role})")
 
 
 def _kab_matrix(identifier, binary_segment_records, value=lambda k: k):

@@ -820,6 +820,37 @@ def gc_pure_vle(table, S, rows, phi, temperature, component=0, order=None, want=
     return out
 
 
+def gc_henry(table, S, rows, phi, temperature, solute=1, order=None, want=("rho_vl", "p_sat", "dlnh_drho", "dpdrho_l", "iters")):
+    """Henry's law constant of molecule `solute` (0 or 1) of every gc row at infinite dilution in the other, pure and saturated,
+    molecule at T [K] (pcs_gc_henry).  table / rows / order as for gc_bubble_dew.  -> dict(h [n] Pa, rho_vl [n,2] (rho_V, rho_L)
+    A^-3 and p_sat [n] Pa of the pure solvent, dlnh_drho [n] A^3 = d ln H / d rho_L, dpdrho_l [n] reduced dp/drho at the liquid
+    root, status bool, iters int32 evaluations, -1 for failed rows); outputs of failed rows are 0.  want: the optional outputs to
+    compute (the others are passed as NULL and left out of the dict); h is always computed."""
+    if isinstance(solute, bool) or solute not in (0, 1):
+        raise ValueError("solute must be 0 or 1 (molecule index)")
+    device = table.device
+    phi = _prep(phi, device, (2,))
+    temperature = _prep(temperature, device)
+    n = temperature.shape[0]
+    _check_gc(table, S, rows, n)
+    _same_rows(n, phi=phi)
+    _check_order(order, n, device)
+    out = {"h": _new(device, n),
+           "rho_vl": _new(device, (n, 2)) if "rho_vl" in want else None,
+           "p_sat": _new(device, n) if "p_sat" in want else None,
+           "dlnh_drho": _new(device, n) if "dlnh_drho" in want else None,
+           "dpdrho_l": _new(device, n) if "dpdrho_l" in want else None}
+    status = _new(device, n, dtype=torch.uint8)
+    iters = _new(device, n, dtype=torch.int32) if "iters" in want else None
+    _call(device, "pcs_gc_henry", int(solute), table, int(S), rows, phi, temperature, n, out["h"], out["rho_vl"], out["p_sat"],
+          out["dlnh_drho"], out["dpdrho_l"], status, iters, order)
+    out = {k: v for k, v in out.items() if v is not None}
+    out["status"] = status.view(torch.bool)
+    if iters is not None:
+        out["iters"] = iters
+    return out
+
+
 def gc_stability(table, S, rows, phi, temperature, density, order=None):
     """mix_stability for gc rows (pcs_gc_stability); order: optional class order of the rows (gc_class_order), schedule
     only.  -> dict(tpd, rho_trial, status)."""

@@ -601,6 +601,40 @@ int pcs_gc_pure_vle(int component, const double* table, int S, const uint8_t* ro
                     int64_t n, double* p_sat, double* rho_vl, double* dpdrho_vl, uint8_t* status, int32_t* iters,
                     const int32_t* order, void* stream);
 
+/*
+ * Henry's law constant of ONE molecule of a gc-PC-SAFT row at infinite dilution in the other, pure and saturated, molecule
+ * (ABI 120): pcs_mix_henry on the gc model, one kernel (csrc/gc_henry.hip on csrc/gc_henry.hpp).  With s the solute, v = 1 - s
+ * the solvent, rho_L the saturated liquid density of molecule v taken as a pure fluid at T (the solve of pcs_gc_pure_vle,
+ * pure_line_vle of csrc/gc_saturation.hpp, unchanged) and mu_s = da/drho_s the residual chemical potential of the row's
+ * two-molecule model at the partial densities rho_v = rho_L, rho_s = 0 (what pcs_gc_derivatives returns as mu):
+ *     H = rho_L k_B T exp(mu_s) = rho_L [A^-3] T k_B 1e30 exp(mu_s)   [Pa],
+ * the fugacity-based constant; the K-factor form y p / x is not computed.  mu_s and d mu_s/d rho_v come from ONE two-variable
+ * evaluation at that state (the evaluation of pcs_gc_derivatives).  The reference has no counterpart.
+ *   solute                0 or 1: the molecule of each row that is infinitely dilute; anything else is an error return
+ *   table, S, rows, phi   in   as for pcs_gc_bubble_dew (rows 16-byte aligned)
+ *   temp      [n]    in   K
+ *   h         [n]    out  Pa                                                                               (required)
+ *   rho_vl    [n,2]  out  (rho_V, rho_L) of the pure solvent in A^-3                                        (optional)
+ *   p_sat     [n]    out  Pa, the pure solvent's saturation pressure, as pcs_gc_pure_vle                    (optional)
+ *   dlnh_drho [n]    out  A^3: d ln H / d rho_L = 1 / rho_L + d mu_s / d rho_v at fixed T and parameters    (optional)
+ *   dpdrho_l  [n]    out  the reduced dp/drho of the pure solvent at the liquid root (> 0)                  (optional)
+ *   status    [n]    out  uint8, 1 = failed; outputs of such rows are 0.  A row fails AT ONCE when T is non-finite or <= 0 or
+ *                         phi is non-finite; otherwise with every failure of pcs_gc_pure_vle on the solvent (no equilibrium
+ *                         at T: every T at or above the solvent's critical temperature), or where H or dlnh_drho is not
+ *                         finite or H <= 0.  A supercritical solute is an ordinary row.
+ *   iters     [n]    out  int32 model evaluations used (the solvent's plus one), -1 for failed rows (optional, diagnostics)
+ *   order     [n]    in   optional class order of the rows as for pcs_gc_bubble_dew (NULL: bucketed by class inside each
+ *                         workgroup); only the schedule changes, results are identical.  One row per lane, no work queue.
+ * A row's result does not depend on the rows it shares a wave with, on n or on order.  Backward pass: two
+ * pcs_gc_derivatives_vjp calls accumulating into one grad_seg, at (rho_V, 0) and (rho_L, 0) on the solvent's column.  With
+ * gH = g H for an upstream gradient g of H, dv = 1/rho_V - 1/rho_L and w = gH dlnh_drho / dpdrho_l:  g_a = -w / (rho_V dv) on
+ * the vapour call;  g_a = +w / (rho_L dv), g_p = -w and g_mu[:, s] = gH on the liquid call;  d H/dT = gH / T + the summed
+ * jac9[:, 6]  (d ln H/d theta = @mu_s/@theta + dlnh_drho d rho_L/d theta, d rho_L/d theta as for pcs_gc_pure_vle).
+ */
+int pcs_gc_henry(int solute, const double* table, int S, const uint8_t* rows, const double* phi, const double* temp, int64_t n,
+                 double* h, double* rho_vl, double* p_sat, double* dlnh_drho, double* dpdrho_l, uint8_t* status, int32_t* iters,
+                 const int32_t* order, void* stream);
+
 /* GcPcSaftMix.derivatives (feos_torch/gc_pcsaft.py:443-468): a, p, mu [n,2], v [n,2] at rho [n,2]. */
 int pcs_gc_derivatives(const double* table, int S, const uint8_t* rows, const double* phi, const double* temp,
                        const double* rho, int64_t n, double* a, double* p, double* mu, double* v, void* stream);

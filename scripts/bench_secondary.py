@@ -39,6 +39,10 @@ with HIP events on the launch stream, inputs resident in HBM.
             either component, at 0.7 x the critical-temperature estimate of gc_batch for that molecule; next to it the liquid
             plus the vapour pcs_gc_density call at the resulting p_sat on the same rows (x = 1 / x = 0), forward + backward
             through the model class, failed rows and the histogram of evaluations per row
+  gc_henry: GcPcSaftMix.henrys_law_constant kernel (pcs_gc_henry) on gc_batch(1e6) in class order, either solute, at 0.7 x the
+            critical-temperature estimate of gc_batch for the SOLVENT; next to it what the same number costs without it --
+            pcs_gc_pure_vle on the solvent plus pcs_gc_derivatives at (rho_L, 0) --, forward + backward through the model class,
+            failed rows
 Prints one JSON object per config."""
 import json
 import os
@@ -456,3 +460,44 @@ if "gc_saturation" in which:
                           "ms_forward_backward_equilibrium_liquid_density": ms_fb_rho, "failed": int(r["status"].sum()),
                           "failed_density_liquid": int((rl["status"] & ok).sum()), "failed_density_vapour": int((rv["status"] & ok).sum()),
                           "evaluations": torch.bincount(r["iters"][ok].long()).tolist()}))
+if "gc_henry" in which:
+    # the launch shape of gc_saturation; the neighbours on the same rows are the two calls the fused kernel replaces
+    from feos_torch_amd import GcPcSaftMix
+    n = 1_000_000
+    table = load_segment_table(os.path.join(ROOT, "tests", "data", "sauer2014_hetero.json"))
+    b = gc_batch(n, table); ident = [s for s, _ in table]
+    par = tuple(torch.tensor([v[k] for _, v in table], dtype=torch.float64, requires_grad=True) for k in range(8))
+    phi_leaf = d(b["phi"]).requires_grad_(True)
+    model = GcPcSaftMix(ident, par, b["segment_lists"], b["bond_lists"], b["kab_list"], phi_leaf)
+    tab, S, rows = model._table(), model.S, model.rows
+    phi = phi_leaf.detach()
+    order = native.gc_class_order(tab, S, rows)
+    seg_par = dict(table)
+    tc_of = {}
+
+    def tc_estimate(segs):  # as in the gc_saturation mode
+        if id(segs) not in tc_of:
+            m = np.array([seg_par[s][0] for s in segs]); e = np.array([seg_par[s][2] for s in segs])
+            tc_of[id(segs)] = (m * e).sum() / m.sum() * 1.28 * m.sum() ** 0.45
+        return tc_of[id(segs)]
+    for solute in (0, 1):
+        v = 1 - solute
+        T = d(0.7 * np.array([tc_estimate(row[v]) for row in b["segment_lists"]]))
+        ms, r = timed(lambda: native.gc_henry(tab, S, rows, phi, T, solute, order=order), reps=5)
+        ms_h, _ = timed(lambda: native.gc_henry(tab, S, rows, phi, T, solute, order=order, want=()), reps=5)
+        ms_vle, vle = timed(lambda: native.gc_pure_vle(tab, S, rows, phi, T, v, order=order), reps=5)
+        zero = torch.zeros_like(T)
+        rho = torch.stack((zero, vle["rho_vl"][:, 1]) if solute == 0 else (vle["rho_vl"][:, 1], zero), dim=1).contiguous()
+        ms_deriv, _ = timed(lambda: native.gc_derivatives(tab, S, rows, phi, T, rho), reps=5)
+
+        def fwd_bwd():
+            model.rows, model.phi, model._order = rows, phi_leaf, order  # the call reduces the model: start from all rows
+            leaf = T.clone().requires_grad_(True)
+            h, _ = model.henrys_law_constant(leaf, solute=solute)
+            h.log().sum().backward()
+            return leaf.grad
+        ms_fb, _ = timed(fwd_bwd, reps=3)
+        print(json.dumps({"config": f"GcPcSaftMix henrys_law_constant solute={solute} batch={n:.0e}", "ms": ms, "rows_per_s": n / ms * 1e3,
+                          "ms_h_only": ms_h, "ms_gc_pure_vle_solvent": ms_vle, "ms_gc_derivatives_at_rho_l": ms_deriv,
+                          "over_the_two_calls": ms / (ms_vle + ms_deriv), "ms_forward_backward": ms_fb, "failed": int(r["status"].sum()),
+                          "failed_gc_pure_vle": int(vle["status"].sum())}))
