@@ -36,40 +36,50 @@ constexpr int K1_BINS = 4;
 // wave they save.  Removed.)
 
 // Staging of k_pure_vle_ordered: position pos of the batch holds row order[pos] (a tile-local permutation as
-// pcs_pure_row_order writes it; a scheduling hint, every row's bits are the same wherever it is solved).  The double2 at tile
-// index idx2 comes from the row at position row0 + (idx2 >> 2): four neighbouring lanes read one whole 64-byte row.  Every
-// entry is bounded by n before it is an index (a foreign or stale array must not fault; an entry out of range stands for
-// its own position); positions past n clamp to position n - 1 and store nothing.  The workgroups of a tile share an XCD
-// (bijective swizzle: hardware workgroup b runs on XCD b % 8 and takes the b / 8-th of that XCD's contiguous share of the
-// grid), so that a tile's lines are fetched into one L2, its scattered stores merge there, and every XCD sees every class --
-// with the plain mapping workgroup k of every 8-workgroup stretch of a class-ordered tile lands on the same XCD and the XCDs
-// that only ever get polar + associating rows set the launch's time (measured on host-permuted input: 0.92 of the unsorted
-// batch without the grouping, 1.07-1.18 with it).
-// -> the row of lane t, -1 for a lane past n; its parameters and T are staged at lds[t * STAGE_ROW_PAD], behind the barrier.
-__device__ __forceinline__ int64_t ordered_stage(const double* __restrict__ params, const double* __restrict__ temp, int64_t n,
-                                                 const int32_t* __restrict__ order, double* lds) {
-    const int t = threadIdx.x;
+// pcs_pure_row_order writes it; a scheduling hint, every row's bits are the same wherever it is solved).  Lane t solves the
+// row at position row0 + t.  Every entry is bounded by n before it is an index (a foreign or stale array must not fault; an
+// entry out of range stands for its own position); positions past n clamp to position n - 1 and store nothing.  The
+// workgroups of a tile share an XCD (bijective swizzle: hardware workgroup b runs on XCD b % 8 and takes the b / 8-th of
+// that XCD's contiguous share of the grid), so that a tile's lines are fetched into one L2, its scattered stores merge
+// there, and every XCD sees every class -- with the plain mapping workgroup k of every 8-workgroup stretch of a
+// class-ordered tile lands on the same XCD and the XCDs that only ever get polar + associating rows set the launch's time
+// (measured on host-permuted input: 0.92 of the unsorted batch without the grouping, 1.07-1.18 with it).
+// Workgroup-uniform values (the swizzle, row0, the tile's share of order[]) come from blockIdx / gridDim alone and live in
+// scalar registers; per-lane indices are 32 bits wide (the host's enter() returns for n == 0 and refuses n >= 2^31 before
+// any launch, so n - 1 below is a valid row).  Each lane reads and bounds ONE entry of order[], that of its own position,
+// fetches its own 64-byte row with four 16-byte loads off one address and stages it, with T, for itself: no exchange of
+// indices between lanes and no workgroup barrier (the loads of a wave touch 64 lines instead of 16, which this kernel,
+// bound by VALU issue, does not notice on the bench batch: profiles/ordered_stage.md).  The row and T still go through LDS:
+// the solve re-reads the row there instead of holding it in registers, and T arrives as the LDS load it is in k_pure_vle.
+// The wave-level fence keeps the compiler from forwarding the stores to the loads.  Both are load-bearing for the
+// bit-for-bit pins (tests/test_pure_row_order_gpu.py, test_pure_ordered_stage_gpu.py, test_model_shell_gpu.py): this unit
+// is built with -fassociative-math, and with T handed over in a register (a global load) the compiler orders the products
+// T enters differently -- measured: p_sat moves in the last bit on 2.3 % of the rows; without the fence the row never
+// reaches LDS and it is 3.9 %.  Do not remove the fence or the pad-slot T without re-running those tests.
+// -> the row of lane t, -1 for a lane past n; its parameters and T are staged at lds[t * STAGE_ROW_PAD].
+__device__ __forceinline__ int ordered_stage(const double* __restrict__ params, const double* __restrict__ temp, int64_t n,
+                                             const int32_t* __restrict__ order, double* lds) {
+    const unsigned t = threadIdx.x;
     const unsigned b = blockIdx.x, nwg = gridDim.x, xcd = b % 8u, q = nwg / 8u, rem = nwg % 8u;
     const unsigned wg = (xcd < rem ? xcd * (q + 1u) : rem * (q + 1u) + (xcd - rem) * q) + b / 8u;
-    const int64_t row0 = (int64_t)wg * STAGE_BLOCK;
-    auto row_at = [=](int64_t pos) -> int64_t {
-        if (pos > n - 1) pos = n - 1;
-        const int64_t r = order[pos];
-        return (r >= 0 && r < n) ? r : pos;
-    };
-    const double2* src = reinterpret_cast<const double2*>(params);
+    const unsigned rows = (unsigned)n, row0 = min(wg * (unsigned)STAGE_BLOCK, rows - 1u);
+    const unsigned last = rows - 1u - row0;  // row n - 1 as a position of this tile
+    const unsigned pos = min(t, last);
+    const unsigned entry = (unsigned)(order + row0)[pos];
+    const unsigned i = entry < rows ? entry : row0 + pos;  // one unsigned test bounds both sides
+    const double2* src = reinterpret_cast<const double2*>(params) + (uint64_t)i * 4u;
+    double* mine = lds + t * STAGE_ROW_PAD;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int idx2 = t + k * STAGE_BLOCK;
-        const int r = idx2 >> 2, c2 = idx2 & 3;
-        const double2 v = src[row_at(row0 + r) * 4 + c2];
-        lds[r * STAGE_ROW_PAD + 2 * c2] = v.x;
-        lds[r * STAGE_ROW_PAD + 2 * c2 + 1] = v.y;
+        const double2 v = src[k];
+        mine[2 * k] = v.x;
+        mine[2 * k + 1] = v.y;
     }
-    const int64_t i = row_at(row0 + t);
-    lds[t * STAGE_ROW_PAD + 8] = temp[i];
-    __syncthreads();
-    return row0 + t < n ? i : -1;
+    mine[8] = temp[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return t <= last ? (int)i : -1;
 }
 
 // Bucket key of a staged row: model class (which branches of the Helmholtz energy the row needs) in
@@ -104,11 +114,12 @@ __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
     __shared__ int bins[K1_BINS];
     const int t = threadIdx.x;
     if constexpr (ORDERED) {
-        const int64_t i = ordered_stage(params, temp, n, order, lds);
+        const int row = ordered_stage(params, temp, n, order, lds);
         VleResult res;
         const double T = lds[t * STAGE_ROW_PAD + 8];
         const int st = vle_fast_lite<POLISH, RHO>(&lds[t * STAGE_ROW_PAD], T, res);
-        if (i < 0) return;
+        if (row < 0) return;
+        const unsigned i = (unsigned)row;
         if (st == ST_OK) {
             if (p_sat) p_sat[i] = res.p_star * T * P_UNIT;
             if (iters) iters[i] = res.iters;
@@ -116,7 +127,7 @@ __device__ __forceinline__ void pure_vle_rows(const double* __restrict__ params,
         } else {
             status[i] = 1;  // provisional; a later pass overwrites it
             const int slot = atomicAdd(&retry[0], 1);
-            if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)((uint32_t)i | (st == ST_FALLBACK ? 0x80000000u : 0u));
+            if (slot >= 0 && slot < n) retry[1 + slot] = (int32_t)(i | (st == ST_FALLBACK ? 0x80000000u : 0u));
         }
         return;
     }
